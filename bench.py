@@ -15,10 +15,13 @@ reference's global counter (total_pckts / total_bytes, sequence.c:12-14,
 over RCCL at the end of the timed region.  Under torchrun the process group is
 created at every world size, 1 included, so the RCCL path runs on one GPU too.
 
-Prints ONE JSON line on rank 0.  The 1500-B variant, the D2H-inclusive rate
-into 4 KiB UMEM slots and the write-roofline probe ride along as extra keys.
-The CPU oracle (oracle/, the checker) is timed beside it on the host cores as
-cpu_baseline — it is never the thing measured.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline
+needs: set up, ramp, warm up, time the steps.  --full adds the rest as extra
+keys: each launch timed on its own in a separate pass, the write-roofline probe,
+the 1500-B variant, the D2H-inclusive rate into 4 KiB UMEM slots, and the CPU
+oracle (oracle/, the checker) timed on the host cores as cpu_baseline — it is
+never the thing measured.  --dump-outputs DIR writes a fixed sample of the frames
+the last timed step built as DIR/<name>.npy, the same from run to run.
 """
 import argparse
 import json
@@ -43,6 +46,10 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level par
 HBM_ACHIEVABLE_GBPS = 6300.0  # the same guide's "≈6.3 TB/s achievable" (HBM section)
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_r06.json")
 MIX = ("c2_udp_64", "c4_tcp_syn", "c5_icmp_echo")  # configs[4]'s three sequences (pb_configs.c5_mix)
+# --dump-outputs: 4 MiB of frame bytes per sequence (16 MiB as float32; configs[4]'s three: 48 MiB)
+DUMP_BYTES_PER_SEQ = 4 << 20
+DUMP_BLOCKS = 64
+DUMP_SEED = 0x5EEDD0B5
 
 
 def parse():
@@ -56,8 +63,13 @@ def parse():
                     help="iterations per launch per GPU (default 2^25; 2^24 per sequence for c5_mix)")
     ap.add_argument("--config", default="c2_udp_64",
                     choices=["c2_udp_64", "c2_udp_1500", "c3_udp_var", "c4_tcp_syn", "c5_icmp_echo", "c5_mix"])
-    ap.add_argument("--no-variants", action="store_true", help="skip the 1500-B / D2H extras")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-launch timing pass, the write-roofline probe, the 1500-B / D2H "
+                         "variants and the CPU baselines (a plain run times the steps and nothing else)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the 1500-B / D2H extras")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's frames as DIR/<name>.npy")
     ap.add_argument("--pmc", default=PMC_FILE, help="committed rocprofv3 --pmc summary giving HBM bytes per launch")
     a = ap.parse_args()
     if a.packets is None:
@@ -109,7 +121,48 @@ def barrier(dist, local):
             torch.cuda.synchronize(local)
 
 
-def run_configs(ctx, names, n_pkts, steps, warmup, rank, world, dist, local, ramp_s=0.0, launch_reps=0):
+def dump_outputs(ctx, out_dir, names, bufs):
+    """What the last timed step left in its frame buffers, as a caller reads it back
+    (pbgpu_copy_offsets / pbgpu_copy_packed), one set of arrays per sequence:
+      <name>.frame_index.npy   float64  which frames of the step's output were sampled
+      <name>.frame_offset.npy  float64  offsets[f] of each sampled frame in the packed buffer
+      <name>.frame_len.npy     float32  its length
+      <name>.frame_bytes.npy   float32  the sampled frames' bytes, back to back
+    A buffer of up to DUMP_BYTES_PER_SEQ is written whole; a larger one as DUMP_BLOCKS runs
+    of consecutive frames: the first frames, the last frames and seeded starts between."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, fb in zip(names, bufs):
+        n = int(fb.f.n_frames)
+        off = fb.offsets()
+        total = int(off[n])
+        if total <= DUMP_BYTES_PER_SEQ:
+            starts, ends = np.array([0], dtype=np.int64), np.array([n], dtype=np.int64)
+        else:
+            per_block = np.uint64(DUMP_BYTES_PER_SEQ // DUMP_BLOCKS)
+            rng = np.random.default_rng(DUMP_SEED)
+            # the last block ends at the last frame; every block holds whole frames within per_block bytes
+            last = int(np.searchsorted(off, off[n] - per_block, side="left"))
+            starts = np.sort(np.concatenate(([0, last], rng.integers(0, n, DUMP_BLOCKS - 2)))).astype(np.int64)
+            ends = np.searchsorted(off, off[starts] + per_block, side="right").astype(np.int64) - 1
+            ends = np.minimum(np.maximum(ends, starts + 1), n)
+        idx = np.concatenate([np.arange(s, e) for s, e in zip(starts, ends)])
+        data = np.empty(int((off[ends] - off[starts]).sum()), dtype=np.uint8)
+        at = 0
+        for s, e in zip(starts, ends):
+            nb = int(off[e] - off[s])
+            rc = ctx.lib.pbgpu_copy_packed(ctx.h, fb.ptr, data[at:].ctypes.data, int(off[s]), nb)
+            if rc != 0:
+                raise SystemExit(f"--dump-outputs: pbgpu_copy_packed of {name} failed ({rc})")
+            at += nb
+        np.save(os.path.join(out_dir, f"{name}.frame_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.frame_offset.npy"), off[idx].astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.frame_len.npy"), (off[idx + 1] - off[idx]).astype(np.float32))
+        np.save(os.path.join(out_dir, f"{name}.frame_bytes.npy"), data.astype(np.float32))
+    ctx.kernel_time()  # drop the offsets pass of a variable-length buffer from the next span
+
+
+def run_configs(ctx, names, n_pkts, steps, warmup, rank, world, dist, local, ramp_s=0.0, launch_reps=0,
+                dump_dir=None):
     """Warm up, then time exactly `steps` steps; a step builds `n_pkts` iterations
     of every sequence in `names` (one launch each).  Returns per-rank timings and
     the all-reduced counters of the timed steps.
@@ -177,6 +230,8 @@ def run_configs(ctx, names, n_pkts, steps, warmup, rank, world, dist, local, ram
     wall = time.perf_counter() - t0
     k_ms, k_n = ctx.kernel_time()
     per_step_launches = max(1, k_n // steps)
+    if dump_dir is not None:  # before the per-launch pass builds further steps into the buffers
+        dump_outputs(ctx, dump_dir, names, bufs)
     # a separate pass with an event pair around every launch: each launch's own device
     # time (median / min / max; the pairs add ~10 us between launches, so `value` and
     # the roofline come from the span above, not from this pass)
@@ -316,7 +371,7 @@ def main():
     ctx = GpuContext(local)
     names = list(MIX) if a.config == "c5_mix" else [a.config]
     res = run_configs(ctx, names, a.packets, a.steps, a.warmup, rank, world, dist, local, a.ramp_seconds,
-                      launch_reps=20)
+                      launch_reps=20 if a.full else 0, dump_dir=a.dump_outputs if rank == 0 else None)
     bps = res["bytes_per_step"]  # frame bytes one step builds on one GPU
     pkts_total = res["packets_per_step"] * a.steps * world
     wall = res["wall_s"]
@@ -325,13 +380,13 @@ def main():
     achieved = bps / (res["span_ms_per_step"] * 1e-3) / 1e9
     extra = {}
     peak_probe = None
-    if rank == 0:
+    if a.full and rank == 0:
         shapes, best = ctx.fill_probe_shapes(bps, 20)
         peak_probe = bps / (shapes[best] * 1e-3) / 1e9
         extra["write_peak_probe_gbps"] = round(peak_probe, 1)
         extra["write_peak_probe_shape"] = best
         extra["write_peak_probe_shapes_gbps"] = {k: round(bps / (v * 1e-3) / 1e9, 1) for k, v in shapes.items()}
-    if not a.no_variants and a.config == "c2_udp_64":
+    if a.full and not a.no_variants and a.config == "c2_udp_64":
         # >= 20 timed steps (~0.15 s of 50-GB launches) after a full clock ramp
         steps15 = max(20, a.steps // 4)
         v = run_configs(ctx, ["c2_udp_1500"], a.packets, steps15, 2, rank, world, dist, local, a.ramp_seconds,
@@ -354,7 +409,7 @@ def main():
             extra["d2h_umem_64B"] = d2h_rate(ctx, 0, a.packets)
             extra["d2h_umem_64B_slot64"] = d2h_rate(ctx, 0, a.packets, 64)
             extra["d2h_umem_1500B"] = d2h_rate(ctx, 1, a.packets)
-    if not a.no_variants and a.config != "c2_udp_64" and a.config != "c5_mix" and rank == 0:
+    if a.full and not a.no_variants and a.config != "c2_udp_64" and a.config != "c5_mix" and rank == 0:
         # the configured sequence (still loaded at index 0) landed into UMEM slots
         extra["d2h_umem"] = d2h_rate(ctx, 0, a.packets)
     ctx.close()
@@ -400,7 +455,7 @@ def main():
         line["global_counters"] = res["counters"]
         line["global_counters"]["sequences"] = names
     line.update(extra)
-    if world == 1 and a.cpu_seconds > 0:
+    if a.full and world == 1 and a.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(names[0], a.cpu_seconds)
         line["cpu_baseline"]["host"] = host_cpu()
         # the other CPU-path points SURVEY.md §8d names: one thread, the integer-only

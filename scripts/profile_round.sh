@@ -20,7 +20,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || exit 1
   echo "tests + smoke ok"
 fi
-[ -z "$SKIP_TRACE" ] && { timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -o run -- python3 bench.py --steps 100 --warmup 10 --cpu-seconds 2 > $OUT/bench_trace.log 2>&1 || { echo TRACE_FAIL; tail -5 $OUT/bench_trace.log; exit 1; }
+[ -z "$SKIP_TRACE" ] && { timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -o run -- python3 bench.py --full --steps 100 --warmup 10 --cpu-seconds 2 > $OUT/bench_trace.log 2>&1 || { echo TRACE_FAIL; tail -5 $OUT/bench_trace.log; exit 1; }
 grep '^{"metric"' $OUT/bench_trace.log > $OUT/bench_under_trace.json
 python3 scripts/trace_summary.py $OUT/bench_trace/run_kernel_trace.csv $OUT/kernel_trace_summary.json
 echo "trace done"; }
@@ -40,7 +40,7 @@ fi
 [ -n "$SKIP_CFG" ] && exit 0
 for cfg in c2_udp_64 c2_udp_1500 c3_udp_var c4_tcp_syn c5_icmp_echo c5_mix; do
   V=--no-variants; [ $cfg = c3_udp_var ] && V=
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg/trace_$cfg -o run -- python3 bench.py --steps 50 --warmup 5 $V --cpu-seconds 0 --config $cfg --pmc $PMC > $OUT/cfg/$cfg.log 2>&1 || { echo "CFG_FAIL $cfg"; tail -5 $OUT/cfg/$cfg.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg/trace_$cfg -o run -- python3 bench.py --full --steps 50 --warmup 5 $V --cpu-seconds 0 --config $cfg --pmc $PMC > $OUT/cfg/$cfg.log 2>&1 || { echo "CFG_FAIL $cfg"; tail -5 $OUT/cfg/$cfg.log; exit 1; }
   grep '^{"metric"' $OUT/cfg/$cfg.log > $OUT/cfg/$cfg.json
   python3 scripts/trace_summary.py $OUT/cfg/trace_$cfg/run_kernel_trace.csv $OUT/cfg/trace_${cfg}_summary.json 50 > /dev/null
   python3 -c "import json; d=json.load(open('$OUT/cfg/$cfg.json')); r=d['roofline']; t=json.load(open('$OUT/cfg/trace_${cfg}_summary.json'))[0]; print('$cfg', r['kernel'], 'span', r['kernel_ms_avg'], 'trace', round(t['avg_ms'], 5), r['achieved'], 'GB/s', r['frac'], d['write_peak_probe_gbps'], r['traffic'])"

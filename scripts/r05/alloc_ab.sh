@@ -14,7 +14,8 @@ for r in $(seq 1 $REPS); do
       [ $mode = malloc ] && export PBGPU_ALLOC=malloc
       [ $mode = vmm2 ] && export PBGPU_ALLOC_CHUNK_MB=2
       V=--no-variants; [ $cfg = c2_udp_64 ] && V=
-      timeout -k 10 240 python3 bench.py --steps 50 --warmup 5 --cpu-seconds 0 --config $cfg $V > gpurun_out/r05/alloc_ab_last.log 2>&1 || { echo "FAIL $mode $cfg"; tail -5 gpurun_out/r05/alloc_ab_last.log; exit 1; }
+      last=${out%.jsonl}_last.log  # --full: the summary below reads the 1500-B leg
+      timeout -k 10 240 python3 bench.py --full --steps 50 --warmup 5 --cpu-seconds 0 --config $cfg $V > $last 2>&1 || { echo "FAIL $mode $cfg"; tail -5 $last; exit 1; }
       python3 - "$mode" "$cfg" "$r" >> $out <<'PY'
 import json, sys
 mode, cfg, r = sys.argv[1:]

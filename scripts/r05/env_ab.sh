@@ -10,7 +10,8 @@ for r in $(seq 1 ${REPS:-2}); do
   for v in $VALUES; do
     unset $VAR
     [ "$v" != unset ] && export $VAR=$v
-    timeout -k 10 240 python3 bench.py --steps 50 --warmup 5 --cpu-seconds 0 --no-variants --config $CFG > gpurun_out/r05/env_ab_last.log 2>&1 || { echo "FAIL $VAR=$v"; tail -5 gpurun_out/r05/env_ab_last.log; exit 1; }
+    last=${out%.jsonl}_last.log  # --full: the summary below reads the per-launch pass
+    timeout -k 10 240 python3 bench.py --full --steps 50 --warmup 5 --cpu-seconds 0 --no-variants --config $CFG > $last 2>&1 || { echo "FAIL $VAR=$v"; tail -5 $last; exit 1; }
     python3 - "$VAR" "$v" "$r" >> $out <<'PY'
 import json, sys
 var, v, r = sys.argv[1:]

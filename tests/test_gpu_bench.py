@@ -24,7 +24,7 @@ def _line(out):
 
 
 def test_bench_json_line():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--packets",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--packets",
            str(1 << 20), "--ramp-seconds", "0.05", "--cpu-seconds", "0.4"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -61,6 +61,50 @@ def test_bench_json_line():
     shapes = d["write_peak_probe_shapes_gbps"]
     assert len(shapes) == 15 and d["write_peak_probe_shape"] in shapes
     assert d["write_peak_probe_gbps"] == max(shapes.values())
+
+
+@pytest.mark.parametrize("config, n", [("c2_udp_64", 1 << 18), ("c3_udp_var", 1 << 15)])
+def test_bench_plain_run_times_the_steps_and_dumps_them(tmp_path, config, n):
+    """A run without --full: the same headline keys, none of the extra legs; --dump-outputs
+    writes a sample (the buffers here exceed the whole-buffer limit) of the last timed step's
+    frames, equal byte for byte to the oracle's frames of that step's iterations."""
+    import numpy as np
+
+    import oracle_binding as ob
+    import pb_configs as pc
+    import pb_dist
+    from pbgpu import Sequence
+
+    steps, warmup = 3, 1
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--packets", str(n), "--ramp-seconds", "0.05", "--config", config, "--dump-outputs",
+           str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _line(out)
+    assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["unit"] == "Mpps" and d["higher_is_better"] is True and d["dtype"] == "u8" and d["steps"] == steps
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+    for k in ("cpu_baseline", "cpu_baseline_variants", "udp_1500", "d2h_umem", "d2h_umem_64B",
+              "write_peak_probe_gbps"):
+        assert k not in d, k
+    assert d["roofline"]["per_launch_ms"] is None and d["roofline"]["kernel_ms_avg"] > 0
+
+    a = {k: np.load(tmp_path / f"{config}.{k}.npy")
+         for k in ("frame_index", "frame_offset", "frame_len", "frame_bytes")}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(f"{config}.{k}.npy" for k in a)
+    assert a["frame_index"].dtype == a["frame_offset"].dtype == np.float64
+    assert a["frame_len"].dtype == a["frame_bytes"].dtype == np.float32
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    first = pb_dist.step_first_iter(warmup + steps - 1, 0, 1, n)
+    o_data, o_off = ob.build(Sequence.from_config(pc.get(config)), 0, first, n, pc.SEED_BASE)
+    idx = a["frame_index"].astype(np.int64)
+    assert 0 < len(idx) < n and idx[0] == 0 and idx[-1] == n - 1
+    assert np.array_equal(a["frame_offset"], o_off[idx].astype(np.float64))
+    lens = (o_off[idx + 1] - o_off[idx]).astype(np.int64)
+    assert np.array_equal(a["frame_len"], lens.astype(np.float32))
+    want = np.concatenate([o_data[int(o_off[f]):int(o_off[f + 1])] for f in idx])
+    assert np.array_equal(a["frame_bytes"], want.astype(np.float32))
 
 
 def _free_port():
