@@ -158,6 +158,41 @@ int pbgpu_land_wait(pbgpu_ctx *ctx, uint32_t keep);
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes);
 int pbgpu_host_unregister(pbgpu_ctx *ctx, void *ptr);
 
+/* ---- verification: check built (or uploaded) frames on the device ---- */
+#define PBGPU_VERIFY_IP_CSUM 1u   /* IPv4 header words fold to 0xFFFF            */
+#define PBGPU_VERIFY_TOT_LEN 2u   /* tot_len == frame length - 14                */
+#define PBGPU_VERIFY_L4_CSUM 4u   /* L4 segment (+ pseudo header for proto 6/17) */
+#define PBGPU_VERIFY_ALL     7u
+#define PBGPU_VERIFY_SHORT   8u   /* code bit only: frame shorter than 34 B; always checked */
+
+typedef struct pbgpu_verify_result {
+    uint64_t n_checked;
+    uint64_t n_bad;        /* frames failing at least one enabled check            */
+    uint64_t bad_short, bad_ip_csum, bad_tot_len, bad_l4_csum;  /* per check        */
+    uint64_t first_bad;    /* lowest failing frame index, UINT64_MAX if none        */
+    double   device_ms;    /* device time of the verify launches (HIP events)       */
+} pbgpu_verify_result;
+
+/* Checks frames [first_frame, first_frame + n) of a built or uploaded buffer as the CPU checker's
+ * verify_one does (Ethernet + IPv4 without options; the IPv4 header is the 20 bytes at 14, the
+ * protocol byte 23; protocols 6 and 17 add the pseudo header; a stored UDP checksum of 0 gets no
+ * special case).  A frame shorter than 34 B is bad (SHORT) whatever `checks` says and nothing else
+ * is evaluated for it.  codes_out[j] (host memory, n bytes, or NULL) = the OR of the failed bits
+ * of frame first_frame + j; first_bad is an index into the buffer.  Ordered on the context's
+ * stream after the build or upload of `frames`; returns with the result.  Reads no environment
+ * variable and never writes to frames->data.  -EINVAL: a range past n_frames, res == NULL, a
+ * buffer never built or uploaded. */
+int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uint64_t n,
+                 uint32_t checks, pbgpu_verify_result *res, uint8_t *codes_out);
+/* Puts the caller's n frames into an allocated buffer, packed as a build packs them: frame j is
+ * host_data[host_offsets[j] - host_offsets[0] ..] (n + 1 entries), or with host_offsets == NULL
+ * host_data[j * fixed_len ..].  Fills n_frames, fixed_len (0 with host_offsets), total_bytes and
+ * the device offsets[]; the buffer then behaves as a built one for pbgpu_verify and the landing
+ * calls.  Synchronous.  -ENOSPC: buffer too small; -EINVAL: decreasing offsets, a frame longer
+ * than PB_MAX_PCKT_LEN, neither offsets nor a fixed length. */
+int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *frames, const void *host_data,
+                        const uint64_t *host_offsets, uint32_t fixed_len, uint64_t n);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -197,6 +232,10 @@ int pbgpu_fill_probe_ex(pbgpu_ctx *ctx, uint64_t bytes, uint32_t reps, double *m
  * write rate of each shape at that buffer's physical placement. */
 int pbgpu_fill_probe_at(pbgpu_ctx *ctx, void *dst, uint64_t bytes, uint32_t reps, double *ms_per_shape);
 const char *pbgpu_fill_shape_name(int shape);
+/* Read-only counterpart over the caller's device buffer `src` (16-B aligned): reps launches of one
+ * plain read shape - aligned 16-B loads, 4 KiB per workgroup, an XOR of the loaded words stored
+ * once per workgroup - and their mean device time.  What pbgpu_verify is measured against. */
+int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_t reps, double *ms_per_launch);
 
 /* Name of the frame-build kernel variant a loaded sequence launches
  * (as rocprofv3 reports it). */
@@ -205,7 +244,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
 /* ABI self-description for FFI bindings: sizes / offsets of the structs above.
  * which: 0 sizeof(pb_sequence_t), 1 sizeof(pb_payload_opt_t), 2 sizeof(pbgpu_frames),
  *        3 offsetof(pb_sequence_t, ip.ranges), 4 offsetof(pb_sequence_t, pls),
- *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes);
+ *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
+ *        7 sizeof(pbgpu_verify_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

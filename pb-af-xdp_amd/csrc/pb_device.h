@@ -211,6 +211,34 @@ struct pb_kargs
      (((size_t)(nlines) + 7) & ~(size_t)7) * 2)
 #define PB_VST_LDS(wgf) ((size_t)PB_STAGE_L48 * 8 + PB_VST_PRO + PB_VST_CAP(wgf) * (PB_VST_HVN + 5) * 4 + (PB_VST_CAP(wgf) + 2) * 4)
 
+// ---- verification (pbgpu_verify: pb_vpg_kernel, pb_vst_kernel, pb_vfold_kernel) ----
+// pb_vst_kernel: threads per workgroup (a multiple of 64) and stage bytes per window (+ PB_VS_SLACK:
+// header reads past a last short frame).  Measured side by side at 2^24 frames, 1500 B / configs[2]:
+// 256 x 16 KiB 4.65 / 4.21 ms, 256 x 32 KiB 6.7 / 5.4, 256 x 8 KiB 4.8 / 4.25, 128 x 16 KiB 6.8 / 5.6,
+// 64 x 8 KiB 7.5 / 6.1, 64 x 16 KiB 11.3 / 9.2
+#ifndef PB_VST_WT
+#define PB_VST_WT 256
+#endif
+#ifndef PB_VS_STAGE
+#define PB_VS_STAGE 16384u
+#endif
+#define PB_VS_SLACK 64u
+#define PB_VS_BF_MAX 512u  // ... and the most frames per window
+#define PB_VREC_DW 8       // a workgroup's record: {bad, short, ip, tot_len | l4, 0, first bad lo, hi} (two 16-B stores)
+struct pb_vargs
+{
+    const uint8_t *data;     // frames->data (16-B aligned)
+    const uint64_t *offsets; // frames->offsets (variable length), null for fixed length
+    uint64_t first, n;       // frames [first, first + n)
+    uint32_t fixed_len;
+    uint32_t checks;         // PBGPU_VERIFY_* mask
+    uint32_t wgf;            // pb_vst_kernel: frames per workgroup (a multiple of bf); pb_vpg_kernel: pages per wave
+    uint32_t bf;             // pb_vst_kernel: frames per stage window (a multiple of PB_VST_WT / G, <= PB_VS_BF_MAX)
+    uint64_t page0, npages;  // pb_vpg_kernel: the 4-KiB pages holding the range's bytes
+    uint32_t *rec;           // PB_VREC_DW dwords per workgroup
+    uint8_t *codes;          // CODES variants: one code byte per frame of the range
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

@@ -45,6 +45,9 @@ extern "C" hipError_t pbk_launch_scatter(const uint8_t *src, const uint64_t *off
                                          uint8_t *dst, uint32_t stride, uint16_t *lens, hipStream_t st);
 extern "C" hipError_t pbk_launch_fill(void *dst, uint64_t bytes, int mode, hipStream_t st);
 extern "C" const char *pbk_fill_shape_name(int mode);
+extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
+extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -252,6 +255,9 @@ struct frames_events
     uint2 *d_vpt = nullptr;
     bool packed32 = false;
     uint32_t wf = 0;
+    // pbgpu_frames_upload, variable length: the longest uploaded frame + 1 (what a landing checks
+    // against its slot, in place of the building sequence's longest frame); 0 after a build
+    uint32_t up_max_len1 = 0;
 };
 
 frames_events *frames_ev(pbgpu_frames *f)
@@ -282,6 +288,13 @@ struct pbgpu_ctx
     // memory (h_ctr_sum; d_ctr_sum its device address)
     unsigned long long *h_ctr_sum = nullptr, *d_ctr_sum = nullptr;
     unsigned long long *d_img_ctr = nullptr; // counters of the load-time pb_ximg_kernel page builds (never read)
+    // pbgpu_verify: the workgroups' records, the folded result in mapped pinned host memory (written
+    // by pb_vfold_kernel, as h_ctr_sum is by pb_ctr_read) and the code bytes; each grown on demand
+    uint32_t *d_vfy_rec = nullptr;
+    uint64_t vfy_rec_cap = 0; // records
+    unsigned long long *h_vres = nullptr, *d_vres = nullptr;
+    uint8_t *d_vcodes = nullptr;
+    uint64_t vcodes_cap = 0;
     seq_slot seqs[PB_MAX_SEQUENCES];
     std::vector<timing_pair> pending;
     std::vector<timing_pair> pool;
@@ -797,6 +810,12 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipHostFree(ctx->h_ctr_sum);
     if (ctx->d_img_ctr)
         (void)hipFree(ctx->d_img_ctr);
+    if (ctx->d_vfy_rec)
+        (void)hipFree(ctx->d_vfy_rec);
+    if (ctx->h_vres)
+        (void)hipHostFree(ctx->h_vres);
+    if (ctx->d_vcodes)
+        (void)hipFree(ctx->d_vcodes);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->d_lens)
@@ -1803,6 +1822,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
     }
     fe->last = st;
     fe->packed32 = false;
+    fe->up_max_len1 = 0;
     // a landing queued from this buffer must have read it before the build overwrites it
     if (fe->land_pending)
     {
@@ -2234,6 +2254,240 @@ int pbgpu_copy_offsets(pbgpu_ctx *ctx, const pbgpu_frames *f, uint64_t *dst)
     return PBGPU_OK;
 }
 
+// ---- verification ----
+
+// The verify launch of frames [first, first + n): pb_vpg_kernel for fixed lengths up to 128 B,
+// pb_vst_kernel with G lanes per frame by the mean length otherwise.
+static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint64_t mean, pb_vargs *A, uint32_t *grid)
+{
+    if (f->fixed_len && f->fixed_len <= 128)
+    {
+        const uint64_t b0 = first * f->fixed_len, b1 = (first + n) * f->fixed_len;
+        A->page0 = b0 >> 12;
+        A->npages = ((b1 - 1) >> 12) - A->page0 + 1;
+        uint64_t per = A->npages / 16384; // pages per wave: at least 16384 waves in a large launch
+        per = per < 1 ? 1 : (per > 32 ? 32 : per);
+        A->wgf = (uint32_t)per;
+        *grid = (uint32_t)((A->npages + per - 1) / per);
+        return 0;
+    }
+    const int G = mean <= 192 ? 8 : (mean <= 768 ? 16 : (mean <= 3072 ? 32 : 64));
+    const uint32_t ng = PB_VST_WT / (uint32_t)G;
+    // a window fills the stage (fixed length), or three quarters of it: a variable-length window of
+    // longer frames then still fits (one that does not is summed from global memory)
+    const uint64_t target = f->fixed_len ? PB_VS_STAGE - 16 : PB_VS_STAGE / 4 * 3;
+    uint64_t bf = target / (mean ? mean : 1) / ng * ng;
+    bf = bf < ng ? ng : (bf > PB_VS_BF_MAX ? PB_VS_BF_MAX : bf);
+    uint64_t nw = n / (bf * 16384); // windows per workgroup
+    nw = nw < 1 ? 1 : (nw > 64 ? 64 : nw);
+    A->bf = (uint32_t)bf;
+    A->wgf = (uint32_t)(bf * nw);
+    *grid = (uint32_t)((n + A->wgf - 1) / A->wgf);
+    return G;
+}
+
+int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, uint32_t checks,
+                 pbgpu_verify_result *res, uint8_t *codes_out)
+{
+    if (ctx == NULL || f == NULL || res == NULL || f->reserved == NULL) // reserved: set by the first build or upload
+        return PBGPU_EINVAL;
+    if (first_frame > f->n_frames || n > f->n_frames - first_frame)
+        return PBGPU_EINVAL;
+    memset(res, 0, sizeof *res);
+    res->first_bad = UINT64_MAX;
+    if (n == 0)
+        return PBGPU_OK;
+    res->n_checked = n;
+    if (f->fixed_len && f->fixed_len < 34) // every frame is short: nothing to read
+    {
+        res->n_bad = res->bad_short = n;
+        res->first_bad = first_frame;
+        if (codes_out)
+            memset(codes_out, PBGPU_VERIFY_SHORT, n);
+        return PBGPU_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    uint64_t mean = f->fixed_len;
+    if (!f->fixed_len)
+    {
+        const int mrc = materialize_offsets(ctx, f);
+        if (mrc != PBGPU_OK)
+            return mrc;
+        uint64_t total = 0;
+        const int trc = pbgpu_frames_total(ctx, f, &total);
+        if (trc != PBGPU_OK)
+            return trc;
+        mean = total / f->n_frames;
+    }
+    pb_vargs A;
+    memset(&A, 0, sizeof A);
+    A.data = f->data;
+    A.offsets = f->fixed_len ? nullptr : f->offsets;
+    A.first = first_frame;
+    A.n = n;
+    A.fixed_len = f->fixed_len;
+    A.checks = checks & PBGPU_VERIFY_ALL;
+    uint32_t grid = 0;
+    const int shape = verify_shape(f, first_frame, n, mean, &A, &grid);
+    if (grid > ctx->vfy_rec_cap)
+    {
+        if (ctx->d_vfy_rec)
+            (void)hipFree(ctx->d_vfy_rec);
+        ctx->d_vfy_rec = nullptr;
+        ctx->vfy_rec_cap = 0;
+        if (hipMalloc((void **)&ctx->d_vfy_rec, (size_t)grid * PB_VREC_DW * sizeof(uint32_t)) != hipSuccess)
+            return PBGPU_ENOMEM;
+        ctx->vfy_rec_cap = grid;
+    }
+    if (ctx->h_vres == nullptr)
+    {
+        HIPCHK(hipHostMalloc((void **)&ctx->h_vres, 8 * sizeof(unsigned long long),
+                             hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_vres, ctx->h_vres, 0));
+    }
+    if (codes_out && n > ctx->vcodes_cap)
+    {
+        if (ctx->d_vcodes)
+            (void)hipFree(ctx->d_vcodes);
+        ctx->d_vcodes = nullptr;
+        ctx->vcodes_cap = 0;
+        if (hipMalloc((void **)&ctx->d_vcodes, n) != hipSuccess)
+            return PBGPU_ENOMEM;
+        ctx->vcodes_cap = n;
+    }
+    A.rec = ctx->d_vfy_rec;
+    A.codes = codes_out ? ctx->d_vcodes : nullptr;
+    timing_pair tp;
+    {
+        const int prc = timed_pair(ctx, &tp);
+        if (prc != PBGPU_OK)
+            return prc;
+    }
+    ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
+    HIPCHK(hipEventRecord(tp.a, ctx->stream));
+    HIPCHK(pbk_launch_verify(&A, shape, grid, ctx->stream));
+    HIPCHK(pbk_launch_vfold(ctx->d_vfy_rec, grid, ctx->d_vres, ctx->stream));
+    HIPCHK(hipEventRecord(tp.b, ctx->stream));
+    if (codes_out)
+        HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+    res->n_bad = ctx->h_vres[0];
+    res->bad_short = ctx->h_vres[1];
+    res->bad_ip_csum = ctx->h_vres[2];
+    res->bad_tot_len = ctx->h_vres[3];
+    res->bad_l4_csum = ctx->h_vres[4];
+    res->first_bad = ctx->h_vres[5];
+    res->device_ms = ms;
+    return PBGPU_OK;
+}
+
+int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, const uint64_t *host_offsets,
+                        uint32_t fixed_len, uint64_t n)
+{
+    if (ctx == NULL || f == NULL)
+        return PBGPU_EINVAL;
+    uint64_t total = 0, max_len = 0;
+    if (host_offsets)
+    {
+        for (uint64_t i = 0; i < n; ++i)
+        {
+            if (host_offsets[i + 1] < host_offsets[i] || host_offsets[i + 1] - host_offsets[i] > PB_MAX_PCKT_LEN)
+                return PBGPU_EINVAL;
+            max_len = host_offsets[i + 1] - host_offsets[i] > max_len ? host_offsets[i + 1] - host_offsets[i] : max_len;
+        }
+        total = host_offsets[n] - host_offsets[0];
+        fixed_len = 0;
+    }
+    else
+    {
+        if (fixed_len == 0 || fixed_len > PB_MAX_PCKT_LEN)
+            return PBGPU_EINVAL;
+        total = n * fixed_len;
+    }
+    if (total && host_data == NULL)
+        return PBGPU_EINVAL;
+    if (n > f->capacity_frames || n > 0xFFFFFFFFull || ((total + 15) & ~15ull) > f->capacity_bytes)
+        return PBGPU_ENOSPC;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    frames_events *fe = frames_ev(f);
+    if (fe == NULL)
+        return PBGPU_ENOMEM;
+    // as a build: after the buffer's last build on another stream and the landings queued from it
+    hipStream_t st = ctx->stream;
+    if (fe->last && fe->last != st)
+    {
+        if (fe->moved == nullptr)
+            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fe->moved, fe->last));
+        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
+    }
+    fe->last = st;
+    fe->packed32 = false;
+    fe->up_max_len1 = host_offsets ? (uint32_t)max_len + 1 : 0;
+    if (fe->land_pending)
+    {
+        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
+        fe->land_pending = false;
+    }
+    if (total)
+        HIPCHK(hipMemcpyAsync(f->data, host_data, total, hipMemcpyHostToDevice, st));
+    std::vector<uint64_t> off;
+    if (host_offsets) // frame 0 at byte 0, as a build packs them
+    {
+        off.resize(n + 1);
+        for (uint64_t i = 0; i <= n; ++i)
+            off[i] = host_offsets[i] - host_offsets[0];
+        HIPCHK(hipMemcpyAsync(f->offsets, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    f->first_iter = 0;
+    f->n_frames = n;
+    f->fixed_len = fixed_len;
+    f->total_bytes = total;
+    return mark_built(ctx, f, st);
+}
+
+int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_t reps, double *ms_per_launch)
+{
+    if (ctx == NULL || src == NULL || bytes < 16 || reps == 0 || ((uintptr_t)src & 15u))
+        return PBGPU_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    uint32_t *out = nullptr;
+    HIPCHK(hipMalloc((void **)&out, ((bytes / 16 + 255) / 256) * sizeof(uint32_t)));
+    hipEvent_t a = nullptr, b = nullptr;
+    float ms = 0;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess)
+        e = hipEventCreate(&b);
+    if (e == hipSuccess)
+        e = pbk_launch_read(src, bytes, out, ctx->stream); // warm-up
+    if (e == hipSuccess)
+        e = hipEventRecord(a, ctx->stream);
+    for (uint32_t r = 0; r < reps && e == hipSuccess; ++r)
+        e = pbk_launch_read(src, bytes, out, ctx->stream);
+    if (e == hipSuccess)
+        e = hipEventRecord(b, ctx->stream);
+    if (e == hipSuccess)
+        e = hipEventSynchronize(b);
+    if (e == hipSuccess)
+        e = hipEventElapsedTime(&ms, a, b);
+    if (a)
+        (void)hipEventDestroy(a);
+    if (b)
+        (void)hipEventDestroy(b);
+    (void)hipFree(out);
+    if (e != hipSuccess)
+        return PBGPU_EIO;
+    if (ms_per_launch)
+        *ms_per_launch = ms / reps;
+    return PBGPU_OK;
+}
+
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
 {
     if (ctx == NULL || ptr == NULL)
@@ -2406,9 +2660,11 @@ int pbgpu_copy_to_umem_async(pbgpu_ctx *ctx, const pbgpu_frames *f, void *umem, 
     // a frame longer than a slot would overrun the next slot (or, in the last slot,
     // the UMEM allocation): refused, from the fixed length or the sequence's
     // longest frame (the reference does not check, af_xdp.c:214)
-    if (f->fixed_len ? f->fixed_len > slot_stride
-                     : (f->seq_idx >= PB_MAX_SEQUENCES || !ctx->seqs[f->seq_idx].loaded ||
-                        ctx->seqs[f->seq_idx].max_flen > slot_stride))
+    const frames_events *fu = (const frames_events *)f->reserved;
+    if (f->fixed_len     ? f->fixed_len > slot_stride
+        : fu && fu->up_max_len1 ? fu->up_max_len1 - 1 > slot_stride
+                         : (f->seq_idx >= PB_MAX_SEQUENCES || !ctx->seqs[f->seq_idx].loaded ||
+                            ctx->seqs[f->seq_idx].max_flen > slot_stride))
         return PBGPU_EINVAL;
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
@@ -2776,6 +3032,7 @@ size_t pbgpu_abi_size(int which)
     case 4: return offsetof(pb_sequence_t, pls);
     case 5: return offsetof(pb_sequence_t, pl_cnt);
     case 6: return offsetof(pbgpu_frames, total_bytes);
+    case 7: return sizeof(pbgpu_verify_result);
     default: return 0;
     }
 }

@@ -3849,3 +3849,426 @@ extern "C" hipError_t pbk_launch_fill(void *dst, uint64_t bytes, int mode, hipSt
     }
     return hipGetLastError();
 }
+
+// ======================= verification (pbgpu_verify) =======================
+// The checks of the CPU checker's verify_one (oracle/pb_oracle.c), restated: a frame shorter than
+// 34 B is bad (SHORT) and nothing else of it is looked at; otherwise the 20 IPv4 header bytes at
+// 14 fold to 0xFFFF, tot_len == length - 14, and the L4 segment from byte 34 (plus, for protocols
+// 6 and 17, the pseudo header: bytes 26-33, the protocol, the segment length) folds to 0xFFFF.
+// Read-only: every global load is a whole aligned 16-B load into LDS (or, for frames too long to
+// stage, into registers), the sums are taken from there.  All sums are little-endian 16-bit word
+// sums ("frame domain": the frame's byte 2k is a word's low byte), the byte swap of the checker's
+// big-endian ones: one's-complement sums commute with the swap, and 0xFFFF is its own swap.
+
+// the frame's dword at LDS byte address `byte` (any alignment) of the area dw
+__device__ __forceinline__ uint32_t pb_vdw(const uint32_t *dw, uint32_t byte)
+{
+    return __builtin_amdgcn_alignbyte(dw[(byte >> 2) + 1u], dw[byte >> 2], byte & 3u);
+}
+
+// A frame's code from its sums (frame domain, seg folded): ip = bytes [14, 34), ps = bytes [26, 34),
+// seg = bytes [34, len); tot_len in host order
+__device__ __forceinline__ uint32_t pb_vcode(uint32_t ip, uint32_t ps, uint32_t tot_len, uint32_t proto, uint32_t seg,
+                                             uint32_t len, uint32_t checks)
+{
+    if (len < 34u)
+        return 8u;
+    uint32_t code = 0;
+    if (pb_fold(ip) != 0xFFFFu)
+        code |= 1u;
+    if (tot_len != len - 14u)
+        code |= 2u;
+    if (proto == 6u || proto == 17u)
+        seg += ps + (proto << 8) + pb_bswap16(len - 34u);
+    if (pb_fold(seg) != 0xFFFFu)
+        code |= 4u;
+    return code & checks;
+}
+
+// a wave's tallies (the counts are wave-uniform, first is per lane)
+struct pb_vcount
+{
+    uint32_t bad, sh, ip, tl, l4;
+    uint64_t first;
+};
+
+__device__ __forceinline__ void pb_vtally(pb_vcount &c, bool lead, uint32_t code, uint64_t f)
+{
+    c.bad += (uint32_t)__popcll(__ballot(lead && code != 0));
+    c.sh += (uint32_t)__popcll(__ballot(lead && (code & 8u)));
+    c.ip += (uint32_t)__popcll(__ballot(lead && (code & 1u)));
+    c.tl += (uint32_t)__popcll(__ballot(lead && (code & 2u)));
+    c.l4 += (uint32_t)__popcll(__ballot(lead && (code & 4u)));
+    if (lead && code != 0 && f < c.first)
+        c.first = f;
+}
+
+__device__ __forceinline__ uint64_t pb_vwave_min(uint64_t v)
+{
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+    {
+        const uint64_t o = __shfl_xor(v, dd, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// a workgroup's record: two plain 16-B stores
+__device__ __forceinline__ void pb_vrecord(uint32_t *rec, uint32_t wg, uint32_t bad, uint32_t sh, uint32_t ip,
+                                           uint32_t tl, uint32_t l4, uint64_t first)
+{
+    pb_u32x4 *r = reinterpret_cast<pb_u32x4 *>(rec + (size_t)wg * PB_VREC_DW);
+    r[0] = pb_u32x4{bad, sh, ip, tl};
+    r[1] = pb_u32x4{l4, 0u, (uint32_t)first, (uint32_t)(first >> 32)};
+}
+
+// Fixed length, 34 to 128 B: pb_xsmall_kernel / pb_xpage_kernel's page ownership read backwards.  A
+// wave (one per workgroup, so every barrier is wave-local) takes A.wgf consecutive 4-KiB pages of
+// the buffer; per page it loads the page with four 1-KiB load instructions and the 128 B after it
+// (what a frame starting in the page can reach) into LDS, and one lane per frame starting in the
+// page sums that frame's dwords from LDS, moved to the frame's own alignment by v_alignbyte
+// (60- and 98-B frames start on 4- and 2-B boundaries, odd lengths on any byte).
+template <bool CODES>
+__global__ __launch_bounds__(64) void pb_vpg_kernel(pb_vargs A)
+{
+    __shared__ pb_u32x4 s_pg[PB_XPG / 16 + 10];
+    const uint32_t *dw = reinterpret_cast<const uint32_t *>(s_pg);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t flen = A.fixed_len;
+    const uint32_t nd = (flen + 3u) >> 2;                                 // dwords of a frame (>= 9)
+    const uint32_t tmask = 0xFFFFFFFFu >> (8u * (4u * nd - flen));        // the last one's bytes inside the frame
+    const uint64_t fend = A.first + A.n;
+    const uint64_t lim = (fend * flen + 15ull) & ~15ull;                  // no load at or past this byte
+    const uint64_t pg_a = A.page0 + (uint64_t)blockIdx.x * A.wgf;
+    const uint64_t pg_e = A.page0 + A.npages;
+    const uint64_t pg_b = pg_a + A.wgf < pg_e ? pg_a + A.wgf : pg_e;
+    uint64_t base = pg_a << 12;
+    uint64_t fcur = (base + flen - 1u) / flen; // the first frame starting in the wave's pages
+    if (fcur < A.first)
+        fcur = A.first;
+    pb_vcount c = {0, 0, 0, 0, 0, ~0ull};
+    for (uint64_t pg = pg_a; pg < pg_b; ++pg, base += PB_XPG)
+    {
+        const uint8_t *src = A.data + base;
+        pb_u32x4 v[4], vs = pb_u32x4{0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+        {
+            const uint32_t o = i * 1024u + lane * 16u;
+            v[i] = base + o < lim ? *reinterpret_cast<const pb_u32x4 *>(src + o) : pb_u32x4{0, 0, 0, 0};
+        }
+        if (lane < 8u && base + PB_XPG + lane * 16u < lim)
+            vs = *reinterpret_cast<const pb_u32x4 *>(src + PB_XPG + lane * 16u);
+        // the previous page's frames have been summed before its LDS is overwritten
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+            s_pg[i * 64u + lane] = v[i];
+        if (lane < 8u)
+            s_pg[256u + lane] = vs;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t o0 = (uint32_t)(fcur * flen - base); // < flen: fcur is the first frame starting in the page
+        uint32_t cnt = (PB_XPG - o0 + flen - 1u) / flen;    // frames starting in the page
+        if (fend - fcur < cnt)
+            cnt = (uint32_t)(fend - fcur);
+        for (uint32_t s0 = 0; s0 < cnt; s0 += 64u)
+        {
+            const uint32_t s = s0 + lane;
+            const bool valid = s < cnt;
+            const uint32_t o = o0 + (valid ? s : 0u) * flen;
+            const uint32_t *row = dw + (o >> 2);
+            const uint32_t sh = o & 3u;
+            uint32_t prev = row[3], cur, w;
+            uint32_t ip, ps, seg;
+            // frame dwords 3 .. 8: bytes 12 .. 35
+            cur = row[4], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // bytes 12-15
+            ip = w >> 16;
+            cur = row[5], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // 16-19: tot_len first
+            ip = pb_add_halves(ip, w);
+            const uint32_t tot_len = pb_bswap16(w);
+            cur = row[6], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // 20-23: protocol last
+            ip = pb_add_halves(ip, w);
+            const uint32_t proto = w >> 24;
+            cur = row[7], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // 24-27
+            ip = pb_add_halves(ip, w);
+            ps = w >> 16;
+            cur = row[8], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // 28-31
+            ip = pb_add_halves(ip, w);
+            ps = pb_add_halves(ps, w);
+            cur = row[9], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur; // 32-35
+            if (nd == 9u)
+                w &= tmask;
+            ip += w & 0xFFFFu;
+            ps += w & 0xFFFFu;
+            seg = w >> 16;
+            for (uint32_t t = 9; t < nd; ++t)
+            {
+                cur = row[t + 1u], w = __builtin_amdgcn_alignbyte(cur, prev, sh), prev = cur;
+                if (t == nd - 1u)
+                    w &= tmask;
+                seg = pb_add_halves(seg, w);
+            }
+            const uint32_t code = valid ? pb_vcode(ip, ps, tot_len, proto, pb_fold(seg), flen, A.checks) : 0u;
+            pb_vtally(c, valid, code, fcur + s);
+            if (CODES && valid)
+                A.codes[fcur + s - A.first] = (uint8_t)code;
+        }
+        fcur += cnt;
+    }
+    const uint64_t first = pb_vwave_min(c.first);
+    if (lane == 0)
+        pb_vrecord(A.rec, blockIdx.x, c.bad, c.sh, c.ip, c.tl, c.l4, first);
+}
+
+// Everything else: longer fixed frames and packed variable-length frames at any byte offset.  A
+// workgroup owns A.wgf consecutive frames and takes them in windows of A.bf: the window's byte
+// span, widened to 16-B chunks, is loaded into the LDS stage; then each group of G lanes sums one
+// frame at a time from it: lanes 0-5 of the group take the header dwords (frame aligned, as in
+// pb_vpg_kernel), all lanes the segment's 16-B chunks, on the buffer's even addresses - a frame
+// at an odd address has its folded segment sum byte-swapped instead of being read unaligned.  A
+// window that does not fit the stage (frames up to 65,535 B) is summed from global memory with
+// the same aligned 16-B loads, the edge chunks byte-masked (pb_bytemask); only its frames' first
+// chunks pass through LDS, for the header dwords.
+template <int G, bool CODES>
+__global__ __launch_bounds__(PB_VST_WT) void pb_vst_kernel(pb_vargs A)
+{
+    constexpr uint32_t NG = PB_VST_WT / G, NWV = PB_VST_WT / 64;
+    __shared__ pb_u32x4 s_stage[(PB_VS_STAGE + PB_VS_SLACK) / 16];
+    __shared__ uint32_t s_off[PB_VS_BF_MAX + 1];
+    __shared__ uint32_t s_cnt[NWV][8];
+    const uint32_t *dw = reinterpret_cast<const uint32_t *>(s_stage);
+    const uint32_t tid = threadIdx.x, grp = tid / G, gl = tid % G;
+    const uint64_t fa = (uint64_t)pb_xcd_region(blockIdx.x, gridDim.x) * A.wgf;
+    const uint64_t fe = fa + A.wgf < A.n ? fa + A.wgf : A.n;
+    pb_vcount c = {0, 0, 0, 0, 0, ~0ull};
+    for (uint64_t w0 = fa; w0 < fe; w0 += A.bf)
+    {
+        const uint32_t wn = fe - w0 < A.bf ? (uint32_t)(fe - w0) : A.bf;
+        const uint64_t g0 = A.first + w0;
+        const uint64_t sb = A.offsets ? A.offsets[g0] : g0 * A.fixed_len;
+        const uint64_t eb = A.offsets ? A.offsets[g0 + wn] : (g0 + wn) * A.fixed_len;
+        const uint64_t s16 = sb & ~15ull;
+        const bool staged = eb - s16 <= PB_VS_STAGE;
+        const uint32_t span16 = (uint32_t)((eb - s16 + 15ull) & ~15ull); // < 2^26: bf frames of < 64 KiB
+        const uint8_t *src = A.data + s16;
+        if (w0 != fa)
+            __syncthreads(); // the previous window has been summed
+        for (uint32_t i = tid; i <= wn; i += PB_VST_WT)
+            s_off[i] = (uint32_t)((A.offsets ? A.offsets[g0 + i] : (g0 + i) * A.fixed_len) - s16);
+        if (staged)
+            for (uint32_t ch = tid; ch < (span16 >> 4); ch += PB_VST_WT)
+                s_stage[ch] = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
+        __syncthreads();
+        for (uint32_t r0 = 0; r0 < wn; r0 += NG)
+        {
+            const uint32_t fi = r0 + grp;
+            const bool valid = fi < wn;
+            const uint32_t p = s_off[valid ? fi : 0u], q = s_off[valid ? fi + 1u : 0u];
+            const uint32_t len = q - p;
+            uint32_t hb = p;
+            if (!staged)
+            {
+                // the frame's first four chunks into the group's 64-B slot (a group is inside one wave)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (gl < 4u)
+                {
+                    const uint32_t cb = (p & ~15u) + 16u * gl;
+                    s_stage[grp * 4u + gl] =
+                        cb < span16 ? *reinterpret_cast<const pb_u32x4 *>(src + cb) : pb_u32x4{0, 0, 0, 0};
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                hb = grp * 64u + (p & 15u);
+            }
+            uint32_t ip = 0, ps = 0, meta = 0, acc = 0;
+            if (gl < 6u)
+            {
+                const uint32_t w = pb_vdw(dw, hb + 12u + 4u * gl); // frame bytes 12 + 4 gl ..
+                const uint32_t hv = pb_halves(w);
+                if (gl == 0u)
+                    ip = w >> 16;
+                else if (gl == 1u)
+                    ip = hv, meta = pb_bswap16(w); // tot_len
+                else if (gl == 2u)
+                    ip = hv, meta = (w >> 24) << 16; // protocol
+                else if (gl == 3u)
+                    ip = hv, ps = w >> 16;
+                else if (gl == 4u)
+                    ip = hv, ps = hv;
+                else
+                    ip = ps = w & 0xFFFFu;
+            }
+            if (len > 34u)
+            {
+                const uint32_t lo = p + 34u, hi = q;
+                const uint32_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
+                for (uint32_t ch = c0 + gl; ch <= c1; ch += G)
+                {
+                    pb_u32x4 v;
+                    if (staged)
+                        v = s_stage[ch];
+                    else
+                        v = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
+                    if (ch == c0 || ch == c1)
+                    {
+                        const int a = (int)lo - (int)(16u * ch), b = (int)hi - (int)(16u * ch);
+                        v.x &= pb_bytemask(a, b, 0);
+                        v.y &= pb_bytemask(a, b, 1);
+                        v.z &= pb_bytemask(a, b, 2);
+                        v.w &= pb_bytemask(a, b, 3);
+                    }
+                    acc = pb_add_halves(acc, v.x);
+                    acc = pb_add_halves(acc, v.y);
+                    acc = pb_add_halves(acc, v.z);
+                    acc = pb_add_halves(acc, v.w);
+                }
+            }
+            acc = pb_group_sum<G>(acc);
+            ip = pb_group_sum<G>(ip);
+            ps = pb_group_sum<G>(ps);
+            meta = pb_group_sum<G>(meta);
+            uint32_t seg = pb_fold(acc);
+            if (p & 1u) // the sum was taken on the buffer's even addresses (s16 is even)
+                seg = pb_bswap16(seg);
+            const bool lead = valid && gl == 0u;
+            const uint32_t code = lead ? pb_vcode(ip, ps, meta & 0xFFFFu, meta >> 16, seg, len, A.checks) : 0u;
+            pb_vtally(c, lead, code, g0 + fi);
+            if (CODES && lead)
+                A.codes[w0 + fi] = (uint8_t)code;
+        }
+    }
+    const uint64_t first = pb_vwave_min(c.first);
+    if ((tid & 63u) == 0)
+    {
+        uint32_t *r = s_cnt[tid >> 6];
+        r[0] = c.bad, r[1] = c.sh, r[2] = c.ip, r[3] = c.tl, r[4] = c.l4;
+        r[6] = (uint32_t)first, r[7] = (uint32_t)(first >> 32);
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        uint32_t t[5];
+        uint64_t mn = ~0ull;
+        for (uint32_t k = 0; k < 5; ++k)
+        {
+            t[k] = 0;
+            for (uint32_t w = 0; w < NWV; ++w)
+                t[k] += s_cnt[w][k];
+        }
+        for (uint32_t w = 0; w < NWV; ++w)
+        {
+            const uint64_t m = s_cnt[w][6] | (uint64_t)s_cnt[w][7] << 32;
+            mn = m < mn ? m : mn;
+        }
+        pb_vrecord(A.rec, blockIdx.x, t[0], t[1], t[2], t[3], t[4], mn);
+    }
+}
+
+// The workgroups' records folded by one workgroup into mapped pinned host memory (as pb_ctr_read
+// does): out = {bad, short, ip, tot_len, l4, first bad}
+__global__ __launch_bounds__(256) void pb_vfold_kernel(const uint32_t *rec, uint32_t nrec, unsigned long long *out)
+{
+    uint64_t t[5] = {0, 0, 0, 0, 0}, mn = ~0ull;
+    for (uint32_t i = threadIdx.x; i < nrec; i += 256u)
+    {
+        const pb_u32x4 *r = reinterpret_cast<const pb_u32x4 *>(rec + (size_t)i * PB_VREC_DW);
+        const pb_u32x4 a = r[0], b = r[1];
+        t[0] += a.x, t[1] += a.y, t[2] += a.z, t[3] += a.w, t[4] += b.x;
+        const uint64_t m = b.z | (uint64_t)b.w << 32;
+        mn = m < mn ? m : mn;
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k)
+            t[k] += __shfl_xor(t[k], dd, 64);
+    mn = pb_vwave_min(mn);
+    __shared__ unsigned long long s_t[4][6];
+    if ((threadIdx.x & 63u) == 0)
+    {
+        for (uint32_t k = 0; k < 5; ++k)
+            s_t[threadIdx.x >> 6][k] = t[k];
+        s_t[threadIdx.x >> 6][5] = mn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        for (uint32_t k = 0; k < 5; ++k)
+            out[k] = s_t[0][k] + s_t[1][k] + s_t[2][k] + s_t[3][k];
+        for (uint32_t w = 1; w < 4; ++w)
+            mn = s_t[w][5] < mn ? s_t[w][5] : mn;
+        out[5] = mn;
+    }
+}
+
+// read-only roofline probe: 4 KiB per workgroup, one aligned 16-B load per lane, the loads kept
+// live by one XOR word stored per workgroup
+__global__ __launch_bounds__(256) void pb_read_kernel(const pb_u32x4 *src, uint64_t n16, uint32_t *out)
+{
+    const uint64_t ch = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t x = 0;
+    if (ch < n16)
+    {
+        const pb_u32x4 v = src[ch];
+        x = v.x ^ v.y ^ v.z ^ v.w;
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+        x ^= __shfl_xor(x, dd, 64);
+    __shared__ uint32_t s_x[4];
+    if ((threadIdx.x & 63u) == 0)
+        s_x[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        out[blockIdx.x] = s_x[0] ^ s_x[1] ^ s_x[2] ^ s_x[3];
+}
+
+// shape: 0 pb_vpg_kernel, else pb_vst_kernel's G (8, 16, 32, 64)
+extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t grid, hipStream_t st)
+{
+    const bool codes = A->codes != nullptr;
+#define PBK_VST(G)                                                                              \
+    if (codes)                                                                                  \
+        hipLaunchKernelGGL((pb_vst_kernel<G, true>), dim3(grid), dim3(PB_VST_WT), 0, st, *A);    \
+    else                                                                                        \
+        hipLaunchKernelGGL((pb_vst_kernel<G, false>), dim3(grid), dim3(PB_VST_WT), 0, st, *A);
+    switch (shape)
+    {
+    case 0:
+        if (codes)
+            hipLaunchKernelGGL((pb_vpg_kernel<true>), dim3(grid), dim3(64), 0, st, *A);
+        else
+            hipLaunchKernelGGL((pb_vpg_kernel<false>), dim3(grid), dim3(64), 0, st, *A);
+        break;
+    case 8: PBK_VST(8) break;
+    case 16: PBK_VST(16) break;
+    case 32: PBK_VST(32) break;
+    case 64: PBK_VST(64) break;
+    default: return hipErrorInvalidValue;
+    }
+#undef PBK_VST
+    return hipGetLastError();
+}
+
+extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(pb_vfold_kernel, dim3(1), dim3(256), 0, st, rec, nrec, out);
+    return hipGetLastError();
+}
+
+// out: one word per 4 KiB of `bytes`
+extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st)
+{
+    const uint64_t n16 = bytes / 16;
+    hipLaunchKernelGGL(pb_read_kernel, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, st, (const pb_u32x4 *)src,
+                       n16, out);
+    return hipGetLastError();
+}

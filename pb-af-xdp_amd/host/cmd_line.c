@@ -36,6 +36,7 @@ enum
     OPT_VERYRANDOM,
     OPT_UMEMFRAMES,
     OPT_UMEMSLOT,
+    OPT_VERIFY,
 };
 
 static const struct option af_xdp_opts[] = {
@@ -57,6 +58,7 @@ static const struct option af_xdp_opts[] = {
     {"veryrandom", no_argument, NULL, OPT_VERYRANDOM},
     {"umemframes", required_argument, NULL, OPT_UMEMFRAMES},
     {"umemslot", required_argument, NULL, OPT_UMEMSLOT},
+    {"verify", no_argument, NULL, OPT_VERIFY},
     {NULL, 0, NULL, 0},
 };
 
@@ -133,6 +135,9 @@ void parse_cmd_line_af_xdp(struct cmd_line_af_xdp *c, int argc, char **argv)
             break;
         case OPT_UMEMSLOT:
             c->umem_slot = (uint32_t)strtoul(optarg, NULL, 0);
+            break;
+        case OPT_VERIFY: /* the only store to this field: a caller's struct may predate it */
+            c->verify = 1;
             break;
         default:
             break;

@@ -39,6 +39,9 @@ typedef struct cmd_line_af_xdp
     uint32_t umem_slot;   /* --umemslot S: bytes per frame slot (FRAME_SIZE = 4096, af_xdp.h:24, when 0): the UMEM of
                              umem_frames 4-KiB chunks is cut into slots of S bytes (a power of two, 64..4096), so
                              S = 64 lands 64 frames per chunk, contiguously */
+    int verify;           /* --verify: every built batch is checked on the GPU before it lands (pbgpu_verify).
+                             Last, and written only when --verify is parsed (never by the defaults): a caller
+                             whose struct ends at umem_slot stays valid */
 } cmd_line_af_xdp_t;
 
 void parse_cmd_line_af_xdp(struct cmd_line_af_xdp *cmd_af_xdp, int argc, char **argv);

@@ -81,6 +81,7 @@ static const struct option common_opts[] = {
     {"singlefold", no_argument, NULL, O_SECOND_PASS}, {"pcap", required_argument, NULL, O_SECOND_PASS},
     {"tx", required_argument, NULL, O_SECOND_PASS}, {"veryrandom", no_argument, NULL, O_SECOND_PASS},
     {"umemframes", required_argument, NULL, O_SECOND_PASS}, {"umemslot", required_argument, NULL, O_SECOND_PASS},
+    {"verify", no_argument, NULL, O_SECOND_PASS},
     {NULL, 0, NULL, 0},
 };
 
@@ -178,7 +179,8 @@ static void print_cmd_help(void)
                     "-z --cli => Enables the first sequence/packet override (README.md first-sequence options).\n\n"
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
-                    "--umemframes N --umemslot S\n");
+                    "--umemframes N --umemslot S --verify\n"
+                    "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n");
 }
 
 int main(int argc, char **argv)

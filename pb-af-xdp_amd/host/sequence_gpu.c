@@ -44,6 +44,9 @@ static uint64_t total_bytes[PB_MAX_SEQUENCES];
 static uint64_t claimed_frames[PB_MAX_SEQUENCES]; /* max_pckts quota handed to workers */
 static uint64_t tx_descs[PB_MAX_SEQUENCES], tx_comps[PB_MAX_SEQUENCES], tx_wakeups[PB_MAX_SEQUENCES];
 static uint64_t umem_allocs[PB_MAX_SEQUENCES]; /* UMEMs allocated per sequence (--sharedumem: one) */
+static uint64_t verified_frames[PB_MAX_SEQUENCES], verified_bad[PB_MAX_SEQUENCES]; /* --verify */
+static uint8_t verify_on[PB_MAX_SEQUENCES];
+static volatile uint8_t verify_failed[PB_MAX_SEQUENCES]; /* a bad frame stops every thread of the sequence */
 static time_t start_time[PB_MAX_SEQUENCES];
 static time_t end_time[PB_MAX_SEQUENCES];
 static uint16_t seq_cnt;
@@ -164,6 +167,15 @@ static int gb_unreg(void *h, void *p)
 {
     return pbgpu_host_unregister((pbgpu_ctx *)h, p);
 }
+static int gb_verify(void *h, void *frames, uint32_t checks, uint64_t *n_bad, uint64_t *first_bad)
+{
+    pbgpu_verify_result r;
+    pbgpu_frames *f = (pbgpu_frames *)frames;
+    const int rc = pbgpu_verify((pbgpu_ctx *)h, f, 0, f->n_frames, checks, &r, NULL);
+    if (rc == 0)
+        *n_bad = r.n_bad, *first_bad = r.first_bad;
+    return rc;
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -174,7 +186,8 @@ static void gb_close(void *h)
 }
 
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
-                                         gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count};
+                                         gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
+                                         gb_verify};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -534,8 +547,40 @@ static void *gpu_worker(void *p)
         goto out;
     }
     int done = n_cur == 0 ? 4 : 0; /* 1 max bytes, 2 time, 3 error, 4 quota spent */
-    while (!done && !stop_requested)
+    /* --verify: the sequence's own checksums, checked on the GPU before a batch lands */
+    const uint32_t vchecks = (seq->ip.csum ? PBGPU_VERIFY_IP_CSUM | PBGPU_VERIFY_TOT_LEN : 0u) |
+                             (seq->l4_csum ? PBGPU_VERIFY_L4_CSUM : 0u);
+    if (w->cmd.verify && B->verify == NULL)
     {
+        fprintf(stderr, "[%d] --verify: this frame builder cannot verify.\n", seq_num);
+        last_error = PBGPU_ENOTSUP;
+        goto out;
+    }
+    while (!done && !stop_requested && !verify_failed[w->seq_idx])
+    {
+        if (w->cmd.verify)
+        {
+            uint64_t bad = 0, first_bad = 0;
+            if ((rc = B->verify(ctx, fr[cur], vchecks, &bad, &first_bad)) != 0)
+            {
+                fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+            __atomic_add_fetch(&verified_frames[w->seq_idx], B->n_frames(fr[cur]), __ATOMIC_RELAXED);
+            if (bad)
+            {
+                __atomic_add_fetch(&verified_bad[w->seq_idx], bad, __ATOMIC_RELAXED);
+                fprintf(stderr,
+                        "[%d] Verify failed for sequence #%d: %llu bad frame(s), the first at frame %llu of the batch "
+                        "starting at iteration %llu. Stopping the sequence.\n",
+                        seq_num, seq_num, (unsigned long long)bad, (unsigned long long)first_bad,
+                        (unsigned long long)((step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch));
+                last_error = PBGPU_EIO;
+                verify_failed[w->seq_idx] = 1;
+                break;
+            }
+        }
         /* double buffering: the next batch builds on the GPU while this one lands */
         const uint64_t n_next = claim_iters(w->seq_idx, seq->max_pckts, batch, fpi);
         if (n_next &&
@@ -827,6 +872,7 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     }
     const uint16_t idx = seq_cnt++;
     start_time[idx] = time(NULL);
+    verify_on[idx] = cmd.verify ? 1 : 0;
     shared_umem_t *shared = NULL;
     if (cmd.shared_umem && t_cnt > 0)
     {
@@ -952,6 +998,11 @@ int pb_shutdown_stats(pb_config_t *cfg)
                 i + 1, (unsigned long long)p, (unsigned long long)b, (unsigned long long)(p / secs),
                 (unsigned long long)(b / secs), (long)secs);
     }
+    /* --verify: one more line per sequence, after the reference's */
+    for (int i = 0; i < seq_cnt; ++i)
+        if (verify_on[i])
+            fprintf(stdout, "Verified %llu frames on the GPU: %llu bad.\n", (unsigned long long)verified_frames[i],
+                    (unsigned long long)verified_bad[i]);
     fflush(stdout);
     return last_error;
 }
@@ -981,6 +1032,10 @@ void pb_reset(void)
     memset(umem_allocs, 0, sizeof umem_allocs);
     memset(start_time, 0, sizeof start_time);
     memset(end_time, 0, sizeof end_time);
+    memset(verified_frames, 0, sizeof verified_frames);
+    memset(verified_bad, 0, sizeof verified_bad);
+    memset(verify_on, 0, sizeof verify_on);
+    memset((void *)verify_failed, 0, sizeof verify_failed);
     stop_requested = 0;
 }
 

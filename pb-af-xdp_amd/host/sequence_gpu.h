@@ -87,6 +87,9 @@ typedef struct pb_builder
     /* GPUs present (pbgpu_device_count); NULL: not checked.  seq_send refuses a --gpu / --gpus
      * range past it before starting any thread. */
     int (*device_count)(int *n);
+    /* --verify: the batch in `frames` checked where it was built (pbgpu_verify with `checks`): the
+     * bad frames and the first one's index.  NULL: --verify is refused. */
+    int (*verify)(void *h, void *frames, uint32_t checks, uint64_t *n_bad, uint64_t *first_bad);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

@@ -140,6 +140,29 @@ class Frames(C.Structure):
     ]
 
 
+VERIFY_IP_CSUM = 1
+VERIFY_TOT_LEN = 2
+VERIFY_L4_CSUM = 4
+VERIFY_ALL = 7
+VERIFY_SHORT = 8  # code bit only: a frame shorter than 34 B
+NO_BAD_FRAME = 0xFFFFFFFFFFFFFFFF  # VerifyResult.first_bad when every frame is good
+
+
+class VerifyResult(C.Structure):
+    """pbgpu_verify_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_checked", C.c_uint64),
+        ("n_bad", C.c_uint64),
+        ("bad_short", C.c_uint64),
+        ("bad_ip_csum", C.c_uint64),
+        ("bad_tot_len", C.c_uint64),
+        ("bad_l4_csum", C.c_uint64),
+        ("first_bad", C.c_uint64),
+        ("device_ms", C.c_double),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -290,6 +313,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_fill_probe_ex": (C.c_int, [P, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
         "pbgpu_fill_probe_at": (C.c_int, [P, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
         "pbgpu_fill_shape_name": (C.c_char_p, [C.c_int]),
+        "pbgpu_verify": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyResult), P]),
+        "pbgpu_frames_upload": (C.c_int, [P, FP, P, U64P, C.c_uint32, C.c_uint64]),
+        "pbgpu_read_probe_at": (C.c_int, [P, P, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -359,6 +385,34 @@ class FrameBuffer:
                                                first_frame, n, lens.ctypes.data_as(C.POINTER(C.c_uint16))),
                "copy_to_umem")
         return lens
+
+    def verify(self, first: int = 0, n: Optional[int] = None, checks: int = VERIFY_ALL, codes: bool = False):
+        """Checks frames [first, first + n) on the GPU (n None: to the last frame).  Returns the
+        VerifyResult, and with codes=True also each frame's failed-check bits (np.uint8)."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        res = VerifyResult()
+        out = np.zeros(n if codes else 0, dtype=np.uint8)
+        _check(self.ctx.lib.pbgpu_verify(self.ctx.h, self.ptr, first, n, checks, C.byref(res),
+                                         out.ctypes.data if codes and n else None), "verify")
+        return (res, out) if codes else res
+
+    def upload(self, data, offsets=None, fixed_len: int = 0) -> None:
+        """Puts caller-supplied frames into the buffer, packed: `offsets` (n + 1 entries, frame j
+        at data[offsets[j] - offsets[0]:]) or fixed_len-byte frames back to back."""
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray))
+                                    else data, dtype=np.uint8)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if len(off) < 1:
+                raise ValueError("offsets needs n + 1 entries")
+            n, offp = len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_uint64))
+        else:
+            if fixed_len <= 0:
+                raise ValueError("upload needs offsets or a fixed length")
+            n, offp = len(data) // fixed_len, None
+        _check(self.ctx.lib.pbgpu_frames_upload(self.ctx.h, self.ptr, data.ctypes.data if len(data) else None, offp,
+                                                fixed_len, n), "frames_upload")
 
     def free(self) -> None:
         if self.ptr is not None:
@@ -469,6 +523,12 @@ class GpuContext:
         _check(self.lib.pbgpu_fill_probe_at(self.h, fb.f.data, nbytes, reps, ms), "fill_probe_at")
         names = [self.lib.pbgpu_fill_shape_name(i).decode() for i in range(self.FILL_SHAPES)]
         return {names[i]: float(ms[i]) for i in range(self.FILL_SHAPES)}
+
+    def read_probe_at(self, fb: "FrameBuffer", nbytes: int, reps: int) -> float:
+        """The read probe's mean ms per launch over the first nbytes of a frame buffer's own memory."""
+        ms = C.c_double()
+        _check(self.lib.pbgpu_read_probe_at(self.h, fb.f.data, nbytes, reps, C.byref(ms)), "read_probe_at")
+        return float(ms.value)
 
     def kernel_name(self, idx: int) -> str:
         buf = C.create_string_buffer(96)
