@@ -193,6 +193,41 @@ int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uin
 int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *frames, const void *host_data,
                         const uint64_t *host_offsets, uint32_t fixed_len, uint64_t n);
 
+/* ---- pcap stream: built (or uploaded) frames packed into a capture file's bytes on the device
+ *  ---- */
+#define PBGPU_PCAP_FILE_HEADER 1u  /* stream starts with the 24-B pcap file header            */
+#define PBGPU_PCAP_NSEC        2u  /* nanosecond file magic 0xA1B23C4D and ts_frac in ns;
+                                      else 0xA1B2C3D4 and ts_frac in us                         */
+typedef struct pbgpu_pcap_opts {
+    uint64_t t0_ns;        /* time of index 0, ns since the epoch                               */
+    uint64_t step_ps;      /* picoseconds between consecutive frames (10^12 / pps); 0 = all at t0 */
+    uint64_t first_index;  /* global index of frame first_frame (so batches concatenate exactly) */
+    uint32_t flags;        /* PBGPU_PCAP_*; any other bit: -EINVAL                              */
+    uint32_t reserved;     /* must be 0                                                         */
+} pbgpu_pcap_opts;
+
+/* The stream of frames [first_frame, first_frame + n) of `src`, with H = 24 under FILE_HEADER, else 0:
+ *   file header, little-endian u32 words: magic, 0x00040002, 0, 0, 65535, 1 (as pb_pcap_open writes);
+ *   then for j in [0, n), T = t0_ns + floor((first_index + j) * step_ps / 1000):
+ *     ts_sec = (T / 10^9) mod 2^32, ts_frac = T mod 10^9 (NSEC) or (T mod 10^9) / 1000,
+ *     caplen = len = the frame's length, then the frame's bytes (no snaplen truncation).
+ * nbytes = H + 16 n + the frames' bytes.  pbgpu_pcap_size gives nbytes alone.
+ * pbgpu_pcap_pack writes the stream to dst->data[0, nbytes), zeros from nbytes up to the next
+ * multiple of 16 and nothing past that; dst is an allocated frames buffer used as plain device
+ * bytes: afterwards n_frames = 0, fixed_len = 0, total_bytes = nbytes (pbgpu_verify and the landing
+ * calls see no frames) and pbgpu_copy_packed(ctx, dst, host, 0, nbytes) fetches the stream.  src is
+ * only read.  Runs on the context's stream after the build or upload of src and after earlier work
+ * on dst; returns when the stream is in place.  n == 0: nbytes = H, only the file header written.
+ * -EINVAL: NULL arguments, src never built or uploaded, a range past src->n_frames, src == dst or
+ * overlapping data, unknown flag bits, reserved != 0, (first_index + n - 1) * step_ps >= 2^64 (the
+ * device computes it in 64 bits) or a last timestamp past 2^64 ns.  -ENOSPC: dst->capacity_bytes
+ * below nbytes rounded up to 16. */
+int pbgpu_pcap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                    uint32_t flags, uint64_t *nbytes);
+int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                    const pbgpu_pcap_opts *opts, pbgpu_frames *dst,
+                    uint64_t *nbytes, double *device_ms /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -245,7 +280,7 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  * which: 0 sizeof(pb_sequence_t), 1 sizeof(pb_payload_opt_t), 2 sizeof(pbgpu_frames),
  *        3 offsetof(pb_sequence_t, ip.ranges), 4 offsetof(pb_sequence_t, pls),
  *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
- *        7 sizeof(pbgpu_verify_result);
+ *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

@@ -239,6 +239,26 @@ struct pb_vargs
     uint8_t *codes;          // CODES variants: one code byte per frame of the range
 };
 
+// ---- pcap stream packing (pbgpu_pcap_pack: pb_pcap_kernel) ----
+#define PB_PC_WT 256u                // threads per workgroup: one 16-B chunk each, a 4-KiB page of the stream per step
+#define PB_PC_WIN (PB_PC_WT + 2u)    // records a page can touch (a first partial one + 255 of 16 B, and one more to end the last)
+#define PB_PC_NSEC 2u                // pb_pcargs.flags, as PBGPU_PCAP_NSEC / _FILE_HEADER
+#define PB_PC_FILE_HEADER 1u
+struct pb_pcargs
+{
+    const uint8_t *src;      // src->data (16-B aligned)
+    const uint64_t *offsets; // src->offsets (variable length), null for fixed length
+    uint8_t *dst;            // dst->data (16-B aligned)
+    uint64_t first, n;       // frames [first, first + n)
+    uint32_t fixed_len;
+    pb_div rec;              // fixed length: the record size fixed_len + 16
+    uint32_t flags;
+    uint32_t hdr;            // 24 with the file header, else 0
+    uint32_t per;            // pages per workgroup
+    uint64_t end16;          // stream bytes rounded up to 16: what is written
+    uint64_t t0_ns, step_ps, first_index;
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

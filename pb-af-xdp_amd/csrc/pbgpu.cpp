@@ -48,6 +48,7 @@ extern "C" const char *pbk_fill_shape_name(int mode);
 extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
+extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -2488,6 +2489,168 @@ int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_
     return PBGPU_OK;
 }
 
+// ---- pcap stream packing ----
+
+// Argument checks shared by pbgpu_pcap_size and pbgpu_pcap_pack, then the frames' bytes: from the
+// fixed length, or offsets[first + n] - offsets[first] read back (after materialising them).
+static int pcap_body(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, uint32_t flags, uint64_t *body,
+                     uint64_t *src_end)
+{
+    if (ctx == NULL || src == NULL || src->reserved == NULL) // reserved: set by the first build or upload
+        return PBGPU_EINVAL;
+    if (flags & ~(PBGPU_PCAP_FILE_HEADER | PBGPU_PCAP_NSEC))
+        return PBGPU_EINVAL;
+    if (first > src->n_frames || n > src->n_frames - first)
+        return PBGPU_EINVAL;
+    *body = 0;
+    *src_end = 0;
+    if (n == 0)
+        return PBGPU_OK;
+    if (src->fixed_len)
+    {
+        *body = n * src->fixed_len;
+        *src_end = (first + n) * src->fixed_len;
+        return PBGPU_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    const int mrc = materialize_offsets(ctx, src);
+    if (mrc != PBGPU_OK)
+        return mrc;
+    uint64_t o[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&o[0], src->offsets + first, sizeof o[0], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&o[1], src->offsets + first + n, sizeof o[1], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (o[1] < o[0])
+        return PBGPU_EIO;
+    *body = o[1] - o[0];
+    *src_end = o[1];
+    return PBGPU_OK;
+}
+
+int pbgpu_pcap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, uint32_t flags,
+                    uint64_t *nbytes)
+{
+    if (nbytes == NULL)
+        return PBGPU_EINVAL;
+    uint64_t body = 0, src_end = 0;
+    const int rc = pcap_body(ctx, src, first_frame, n, flags, &body, &src_end);
+    if (rc != PBGPU_OK)
+        return rc;
+    *nbytes = ((flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u) + 16u * n + body;
+    return PBGPU_OK;
+}
+
+int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_pcap_opts *opts,
+                    pbgpu_frames *dst, uint64_t *nbytes, double *device_ms)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL || nbytes == NULL || opts->reserved != 0)
+        return PBGPU_EINVAL;
+    if (src == dst || src->data == NULL || dst->data == NULL)
+        return PBGPU_EINVAL;
+    {
+        // the allocations, the readers' 64-B slack included
+        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
+        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
+        if (s0 < d1 && d0 < s1)
+            return PBGPU_EINVAL;
+    }
+    if (n)
+    {
+        // the device computes (first_index + j) * step_ps and t0_ns + that / 1000 in 64 bits
+        if (opts->first_index > UINT64_MAX - (n - 1))
+            return PBGPU_EINVAL;
+        const uint64_t last = opts->first_index + (n - 1);
+        if (opts->step_ps && last > UINT64_MAX / opts->step_ps)
+            return PBGPU_EINVAL;
+        if (last * opts->step_ps / 1000u > UINT64_MAX - opts->t0_ns)
+            return PBGPU_EINVAL;
+    }
+    uint64_t body = 0, src_end = 0;
+    const int brc = pcap_body(ctx, src, first_frame, n, opts->flags, &body, &src_end);
+    if (brc != PBGPU_OK)
+        return brc;
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    const uint32_t H = (opts->flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u;
+    const uint64_t total = H + 16u * n + body;
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    frames_events *fe = frames_ev(dst);
+    if (fe == NULL)
+        return PBGPU_ENOMEM;
+    // as an upload: after dst's last build on another stream and the landings queued from it
+    hipStream_t st = ctx->stream;
+    if (fe->last && fe->last != st)
+    {
+        if (fe->moved == nullptr)
+            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fe->moved, fe->last));
+        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
+    }
+    fe->last = st;
+    fe->packed32 = false;
+    fe->up_max_len1 = 0;
+    if (fe->land_pending)
+    {
+        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
+        fe->land_pending = false;
+    }
+    dst->first_iter = 0;
+    dst->n_frames = 0;
+    dst->fixed_len = 0;
+    dst->total_bytes = total;
+    float ms = 0;
+    if (end16)
+    {
+        pb_pcargs A;
+        memset(&A, 0, sizeof A);
+        A.src = src->data;
+        A.offsets = src->fixed_len ? nullptr : src->offsets;
+        A.dst = dst->data;
+        A.first = first_frame;
+        A.n = n;
+        A.fixed_len = src->fixed_len;
+        A.rec = make_div(src->fixed_len + 16u);
+        A.flags = opts->flags;
+        A.hdr = H;
+        A.end16 = end16;
+        A.t0_ns = opts->t0_ns;
+        A.step_ps = opts->step_ps;
+        A.first_index = opts->first_index;
+        // pages per workgroup grow with the launch: at least 16384 workgroups in a large one, and a
+        // grid below 2^24 however long the stream
+        const uint64_t npages = (end16 + 4095) >> 12;
+        uint64_t per = npages / 16384;
+        per = per < 1 ? 1 : (per > 32 ? 32 : per);
+        if ((npages + per - 1) / per > (1ull << 24))
+            per = (npages + (1ull << 24) - 1) >> 24;
+        if (per > 0xFFFFFFFFull)
+            return PBGPU_EINVAL;
+        A.per = (uint32_t)per;
+        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        timing_pair tp;
+        {
+            const int prc = timed_pair(ctx, &tp);
+            if (prc != PBGPU_OK)
+                return prc;
+        }
+        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
+        HIPCHK(hipEventRecord(tp.a, st));
+        HIPCHK(pbk_launch_pcap(&A, grid, st));
+        HIPCHK(hipEventRecord(tp.b, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+    }
+    *nbytes = total;
+    if (device_ms)
+        *device_ms = ms;
+    return PBGPU_OK;
+}
+
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
 {
     if (ctx == NULL || ptr == NULL)
@@ -3033,6 +3196,7 @@ size_t pbgpu_abi_size(int which)
     case 5: return offsetof(pb_sequence_t, pl_cnt);
     case 6: return offsetof(pbgpu_frames, total_bytes);
     case 7: return sizeof(pbgpu_verify_result);
+    case 8: return sizeof(pbgpu_pcap_opts);
     default: return 0;
     }
 }

@@ -4272,3 +4272,285 @@ extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t 
                        n16, out);
     return hipGetLastError();
 }
+
+// ---------------- pcap stream packing (pbgpu_pcap_pack) ----------------
+// The stream: the 24-B pcap file header (optional), then per frame a 16-B record header
+// {ts_sec, ts_frac, len, len} and the frame's bytes.  Destination-owned: a workgroup owns `per`
+// consecutive 4-KiB pages of the stream, a lane one aligned 16-B chunk of a page per step, so
+// every byte has one writer and every store is an aligned 16-B store.  A lane finds the record
+// that holds its chunk's first byte (records are at least 16 B, so a chunk touches at most two),
+// computes the header words it needs in registers and fetches frame bytes as aligned source
+// dwords moved into place by v_alignbyte.  Positions in the stream are 64-bit; within a page
+// everything is relative to the record holding the page's first byte and fits 32 bits.
+
+// a record as a lane sees it: record j of the range, frame first + j
+struct pb_pcrec
+{
+    uint64_t off;  // the frame's first byte in src
+    uint32_t len;  // the frame's length; the record is 16 + len bytes
+    uint32_t sec, frac;
+    bool valid;    // false: past the last record (those stream bytes are zero)
+    bool fh;       // record 0 of a stream with a file header: the header is its bytes -24 .. -1
+};
+
+// T = t0 + floor(index * step / 1000) ns: once per record a lane touches the header of (one or
+// two of a record's 16-B chunks, never a chunk inside the frame's bytes)
+__device__ __forceinline__ void pb_pc_stamp(const pb_pcargs &A, uint64_t j, pb_pcrec &R)
+{
+    const uint64_t T = A.t0_ns + (A.first_index + j) * A.step_ps / 1000ull;
+    const uint64_t s = T / 1000000000ull;
+    const uint32_t ns = (uint32_t)(T - s * 1000000000ull);
+    R.sec = (uint32_t)s;
+    R.frac = (A.flags & PB_PC_NSEC) ? ns : ns / 1000u;
+}
+
+// source bytes [a, a + 4) as a dword, a < end or 0; bytes at and past `end` (the frame's end) are
+// unspecified.  Only aligned dwords holding a byte of the frame are read.
+__device__ __forceinline__ uint32_t pb_pc_src(const uint32_t *w, uint64_t a, uint64_t end)
+{
+    if (a >= end)
+        return 0u;
+    const uint64_t i = a >> 2;
+    const uint32_t sh = (uint32_t)a & 3u;
+    const uint32_t lo = w[i];
+    const uint32_t hi = (sh && (a | 3u) + 1u < end) ? w[i + 1] : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, sh);
+}
+
+// dword i of a record laid out from its own start: 0-3 the header, 4.. the frame, -6..-1 the
+// file header in front of record 0
+__device__ __forceinline__ uint32_t pb_pc_vd(const pb_pcargs &A, const uint32_t *w, const pb_pcrec &R, int i)
+{
+    if (i < 0)
+    {
+        if (!R.fh)
+            return 0u;
+        return i == -6   ? ((A.flags & PB_PC_NSEC) ? 0xA1B23C4Du : 0xA1B2C3D4u)
+               : i == -5 ? 0x00040002u
+               : i == -2 ? 65535u
+               : i == -1 ? 1u
+                         : 0u;
+    }
+    if (!R.valid)
+        return 0u;
+    if (i < 4)
+        return i == 0 ? R.sec : (i == 1 ? R.frac : R.len);
+    return pb_pc_src(w, R.off + 4u * (uint32_t)(i - 4), R.off + R.len);
+}
+
+// record bytes [o, o + 4), o >= -24, as a dword (bytes past the record's end unspecified)
+__device__ __forceinline__ uint32_t pb_pc_dw(const pb_pcargs &A, const uint32_t *w, const pb_pcrec &R, int o)
+{
+    if (o >= 16)
+        return R.valid ? pb_pc_src(w, R.off + (uint32_t)(o - 16), R.off + R.len) : 0u;
+    const int i = o >> 2; // floor
+    const uint32_t s = (uint32_t)o & 3u;
+    const uint32_t lo = pb_pc_vd(A, w, R, i);
+    const uint32_t hi = s ? pb_pc_vd(A, w, R, i + 1) : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, s);
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
+{
+    // variable length: stream positions of PB_PC_WIN records from record j0 on, relative to it
+    // (below 258 * 65551); 0xFFFFFFFF past the end of the range
+    __shared__ uint32_t s_rel[PB_PC_WIN];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+    const uint32_t reclen = A.fixed_len + 16u;
+    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the stream
+    if (p >= A.end16)
+        return;
+    // j0: the record holding the first page's first byte (0 while that byte is in the file header),
+    // d0: that byte's offset in the record
+    const int64_t q0 = (int64_t)p - (int64_t)A.hdr;
+    uint64_t j0 = 0, g0 = 0;
+    const uint64_t ob = VAR ? A.offsets[A.first] : 0;
+    if (q0 > 0)
+    {
+        if (VAR)
+        {
+            // 16 j + offsets[first + j] rises with j: the last j in [0, n] at or below q0
+            uint64_t lo = 0, hi = A.n;
+            while (lo < hi)
+            {
+                const uint64_t mid = lo + (hi - lo + 1) / 2;
+                if (16u * mid + (A.offsets[A.first + mid] - ob) <= (uint64_t)q0)
+                    lo = mid;
+                else
+                    hi = mid - 1;
+            }
+            j0 = lo;
+            g0 = 16u * lo + (A.offsets[A.first + lo] - ob);
+        }
+        else
+        {
+            j0 = (uint64_t)q0 / reclen; // the one 64-bit division, once per workgroup
+            g0 = j0 * reclen;
+        }
+    }
+    int32_t d0 = (int32_t)(q0 - (int64_t)g0);
+    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
+    bool have_win = false;
+    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    {
+        // variable length: the window of record positions is kept from page to page (d0 then grows
+        // by 4096 a page) and moved only when it no longer reaches the record after the page's last
+        // byte; moved to the record holding the page's first byte it always does (PB_PC_WIN)
+        if (VAR && (!have_win || (int64_t)s_rel[PB_PC_WIN - 1u] <= (int64_t)d0 + 4095))
+        {
+            if (have_win) // d0 >= 4096 - 24 here, and inside the window
+            {
+                uint32_t lo = 0, hi = PB_PC_WIN - 1u;
+                while (lo < hi)
+                {
+                    const uint32_t mid = (lo + hi + 1u) >> 1;
+                    if (s_rel[mid] <= (uint32_t)d0)
+                        lo = mid;
+                    else
+                        hi = mid - 1u;
+                }
+                j0 += lo;
+                d0 -= (int32_t)s_rel[lo];
+            }
+            __syncthreads(); // the window's readers are done
+            offj0 = A.offsets[A.first + (j0 < A.n ? j0 : A.n)];
+            for (uint32_t k = tid; k < PB_PC_WIN; k += PB_PC_WT)
+            {
+                const uint64_t jj = j0 + k;
+                s_rel[k] = jj <= A.n ? 16u * k + (uint32_t)(A.offsets[A.first + jj] - offj0) : 0xFFFFFFFFu;
+            }
+            __syncthreads();
+            have_win = true;
+        }
+        const int32_t d = d0 + 16 * (int32_t)tid;
+        const uint64_t pc = p + 16u * tid;
+        if (pc < A.end16)
+        {
+            // k, r: the chunk starts r bytes into record j0 + k
+            uint32_t k = 0;
+            int32_t r = d;
+            if (d > 0)
+            {
+                if (VAR)
+                {
+                    uint32_t lo = 0, hi = PB_PC_WIN - 1u;
+                    while (lo < hi)
+                    {
+                        const uint32_t mid = (lo + hi + 1u) >> 1;
+                        if (s_rel[mid] <= (uint32_t)d)
+                            lo = mid;
+                        else
+                            hi = mid - 1u;
+                    }
+                    k = lo;
+                    r = d - (int32_t)s_rel[k];
+                }
+                else
+                {
+                    k = pb_divq((uint32_t)d, A.rec);
+                    r = d - (int32_t)(k * reclen);
+                }
+            }
+            const uint64_t j = j0 + k;
+            pb_pcrec Ra, Rb;
+            Ra.valid = j < A.n;
+            Ra.fh = j == 0 && (A.flags & PB_PC_FILE_HEADER);
+            Ra.off = 0, Ra.len = 0, Ra.sec = 0, Ra.frac = 0;
+            Rb.valid = false, Rb.fh = false;
+            Rb.off = 0, Rb.len = 0, Rb.sec = 0, Rb.frac = 0;
+            if (Ra.valid)
+            {
+                if (VAR)
+                {
+                    Ra.off = offj0 + (s_rel[k] - 16u * k);
+                    Ra.len = s_rel[k + 1u] - s_rel[k] - 16u;
+                }
+                else
+                {
+                    Ra.off = (A.first + j) * A.fixed_len;
+                    Ra.len = A.fixed_len;
+                }
+                if (r < 16)
+                    pb_pc_stamp(A, j, Ra);
+            }
+            // the record's bytes end `ea` bytes into it; a record past the range has no end
+            const int32_t ea = Ra.valid ? (int32_t)(Ra.len + 16u) : 0x7FFFFFF0;
+            pb_u32x4 v;
+            if (r >= 16 && r + 16 <= ea)
+            {
+                // wholly inside the frame's bytes: four aligned dwords and, off alignment, a fifth,
+                // which still holds a byte of the frame
+                const uint64_t a = Ra.off + (uint32_t)(r - 16);
+                const uint64_t i = a >> 2;
+                const uint32_t sh = (uint32_t)a & 3u;
+                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
+                const uint32_t w4 = sh ? w[i + 4] : 0u;
+                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
+                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
+                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+            }
+            else
+            {
+                if (r + 16 > ea) // the chunk's tail is the next record's head
+                {
+                    Rb.valid = j + 1 < A.n;
+                    if (Rb.valid)
+                    {
+                        if (VAR)
+                        {
+                            Rb.off = offj0 + (s_rel[k + 1u] - 16u * (k + 1u));
+                            Rb.len = s_rel[k + 2u] - s_rel[k + 1u] - 16u;
+                        }
+                        else
+                        {
+                            Rb.off = (A.first + j + 1) * A.fixed_len;
+                            Rb.len = A.fixed_len;
+                        }
+                        pb_pc_stamp(A, j + 1, Rb);
+                    }
+                }
+                uint32_t o4[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                {
+                    const int32_t o = r + 4 * t;
+                    uint32_t x;
+                    if (o + 4 <= ea)
+                        x = pb_pc_dw(A, w, Ra, o);
+                    else if (o >= ea)
+                        x = pb_pc_dw(A, w, Rb, o - ea);
+                    else
+                    {
+                        const uint32_t m = (1u << (8u * (uint32_t)(ea - o))) - 1u; // ea - o in 1..3
+                        x = (pb_pc_dw(A, w, Ra, o) & m) | (pb_pc_dw(A, w, Rb, o - ea) & ~m);
+                    }
+                    o4[t] = x;
+                }
+                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+            }
+            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
+        }
+        // the next page's first byte: 4096 on in the same window, or a whole number of records on
+        if (VAR)
+            d0 += 4096;
+        else
+        {
+            const int32_t dn = d0 + 4096;
+            const uint32_t kn = pb_divq((uint32_t)dn, A.rec);
+            d0 = dn - (int32_t)(kn * reclen);
+            j0 += kn;
+        }
+    }
+}
+
+extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st)
+{
+    if (A->offsets)
+        hipLaunchKernelGGL((pb_pcap_kernel<true>), dim3(grid), dim3(PB_PC_WT), 0, st, *A);
+    else
+        hipLaunchKernelGGL((pb_pcap_kernel<false>), dim3(grid), dim3(PB_PC_WT), 0, st, *A);
+    return hipGetLastError();
+}

@@ -22,6 +22,7 @@
 
 #include "cmd_line.h"
 #include "config_json.h"
+#include "pcap_dump.h"
 #include "sequence_gpu.h"
 
 typedef struct cmd_line
@@ -31,6 +32,11 @@ typedef struct cmd_line
 } cmd_line_t;
 
 static pb_config_t *cfg;
+/* --pcapdump FILE [--pcapt0 NS] (pcap_dump.h): this file's own options, kept out of
+ * struct cmd_line_af_xdp, whose layout other programs bind */
+static const char *pcapdump_path;
+static int pcapt0_set;
+static uint64_t pcapt0_ns;
 
 static void sign_hdl(int sig)
 {
@@ -43,7 +49,7 @@ enum
     O_INTERFACE = 256, O_BLOCK, O_TRACK, O_MAXPCKTS, O_MAXBYTES, O_PPS, O_BPS, O_DELAY, O_THREADS, O_L4CSUM, O_SMAC,
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
-    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS,
+    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0,
 };
 
 static const struct option common_opts[] = {
@@ -82,6 +88,7 @@ static const struct option common_opts[] = {
     {"tx", required_argument, NULL, O_SECOND_PASS}, {"veryrandom", no_argument, NULL, O_SECOND_PASS},
     {"umemframes", required_argument, NULL, O_SECOND_PASS}, {"umemslot", required_argument, NULL, O_SECOND_PASS},
     {"verify", no_argument, NULL, O_SECOND_PASS},
+    {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
     {NULL, 0, NULL, 0},
 };
 
@@ -164,6 +171,8 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
         case O_PFILE: s->pls[0].is_file = (uint8_t)atoi(a); s->pl_cnt = 1; break;
         case O_PSTRING: s->pls[0].is_string = (uint8_t)atoi(a); s->pl_cnt = 1; break;
         case O_TIME: s->time = strtoull(a, NULL, 10); break;
+        case O_PCAPDUMP: pcapdump_path = a; break;
+        case O_PCAPT0: pcapt0_ns = strtoull(a, NULL, 10); pcapt0_set = 1; break;
         default: break;
         }
     }
@@ -179,8 +188,11 @@ static void print_cmd_help(void)
                     "-z --cli => Enables the first sequence/packet override (README.md first-sequence options).\n\n"
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
-                    "--umemframes N --umemslot S --verify\n"
-                    "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n");
+                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS\n"
+                    "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
+                    "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
+                    "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
+                    "1/pps per frame.\n");
 }
 
 int main(int argc, char **argv)
@@ -278,6 +290,18 @@ int main(int argc, char **argv)
                     "(sequence.c:552) reads the other payloads' setup lengths, where the reference reads the previous "
                     "iteration's (quirk B8).\n",
                     i + 1);
+    }
+    if (pcapdump_path) /* no TX path at all: build, pack, write (pcap_dump.h) */
+    {
+        if (pb_pcap_dump_check(cfg, seq_cnt, &cmd_af_xdp) != 0)
+            return EXIT_FAILURE;
+        signal(SIGINT, sign_hdl);
+        signal(SIGTERM, sign_hdl);
+        const int derr = pb_pcap_dump(cfg, seq_cnt, &cmd_af_xdp, pcapdump_path, pcapt0_set, pcapt0_ns);
+        free(cfg);
+        free(argv_cli);
+        pb_config_free();
+        return derr ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     pb_pcap_t *pcap = NULL;
     if (cmd_af_xdp.pcap)

@@ -1,0 +1,294 @@
+/*
+ * pcap_dump.c — pcktbatch-gpu --pcapdump (pcap_dump.h).
+ *
+ * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
+ * Batch k is (verified,) packed into stream buffer k & 1; batch k + 1's build is queued into the
+ * other frame buffer; then stream k is copied to its host buffer in one piece and written with
+ * one write() per buffer (looped only on a short write).
+ */
+#include "pcap_dump.h"
+
+#include <errno.h>
+#include <fcntl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include <unistd.h>
+
+#define PB_DUMP_BATCH_BYTES_MAX (256ull << 20) /* device bytes per frame buffer, as the TX workers' */
+
+int pb_pcap_dump_check(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_xdp *cmd)
+{
+    if (cmd->pcap)
+    {
+        fprintf(stderr, "--pcapdump does not combine with --pcap: one capture per run.\n");
+        return PBGPU_EINVAL;
+    }
+    if (cmd->tx && strcmp(cmd->tx, "xsk") == 0)
+    {
+        fprintf(stderr, "--pcapdump does not combine with --tx xsk: it has no TX path.\n");
+        return PBGPU_EINVAL;
+    }
+    if (cmd->gpus > 1)
+    {
+        fprintf(stderr, "--pcapdump runs on one GPU (--gpu I); --gpus %d given.\n", cmd->gpus);
+        return PBGPU_EINVAL;
+    }
+    for (int i = 0; i < seq_cnt; ++i)
+    {
+        const pb_sequence_t *s = &cfg->seq[i];
+        if (s->max_bytes || s->time)
+        {
+            fprintf(stderr, "[%d] --pcapdump stops on a packet count only: %s is set.\n", i + 1,
+                    s->max_bytes ? "max bytes" : "time");
+            return PBGPU_EINVAL;
+        }
+        if (s->max_pckts == 0)
+        {
+            fprintf(stderr, "[%d] --pcapdump needs a packet count (--maxpckts / \"maxpckts\") above 0.\n", i + 1);
+            return PBGPU_EINVAL;
+        }
+    }
+    return PBGPU_OK;
+}
+
+static int write_all(int fd, const uint8_t *p, uint64_t n)
+{
+    while (n)
+    {
+        const ssize_t w = write(fd, p, n);
+        if (w < 0)
+        {
+            if (errno == EINTR)
+                continue;
+            return -1;
+        }
+        p += w;
+        n -= (uint64_t)w;
+    }
+    return 0;
+}
+
+typedef struct dump_state
+{
+    pbgpu_ctx *ctx;
+    int fd;
+    int header_due; /* the run's first pack carries the file header */
+    const struct cmd_line_af_xdp *cmd;
+    const char *device;
+} dump_state_t;
+
+/* One sequence: frames [0, max_pckts) stamped from t0_ns; *n_done = the frames written. */
+static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx, uint64_t t0_ns, uint64_t step_ps,
+                         uint64_t *n_done, uint64_t *n_verified, uint64_t *n_bad)
+{
+    const int seq_num = idx + 1;
+    pbgpu_ctx *ctx = D->ctx;
+    pbgpu_frames *src[2] = {NULL, NULL}, *dst[2] = {NULL, NULL};
+    uint8_t *hb[2] = {NULL, NULL};
+    int reg[2] = {0, 0};
+    int rc;
+    uint64_t done = 0, iter = 0; /* frames written; the current batch's first iteration */
+    pb_rules_t rules;
+    uint8_t smac[6], dmac[6];
+    pb_seq_prepare(seq, D->device, D->cmd, seq_num, &rules, smac, dmac);
+    if ((rc = pbgpu_load_sequence(ctx, idx, seq, smac, dmac, &rules, D->cmd->seed_base)) != 0)
+    {
+        fprintf(stderr, "[%d] Error loading sequence on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first, pbgpu_strerror(rc));
+        return rc;
+    }
+    const uint32_t fpi = seq->pl_cnt < 1 ? 1u : seq->pl_cnt;
+    const uint64_t quota = seq->max_pckts;
+    uint64_t batch = D->cmd->gpu_batch ? D->cmd->gpu_batch : (1u << 20);
+    if (batch > (quota + fpi - 1) / fpi)
+        batch = (quota + fpi - 1) / fpi;
+    uint64_t mf = 0, mb = 0;
+    for (;;)
+    {
+        if ((rc = pbgpu_build_size(ctx, idx, batch, &mf, &mb)) != 0)
+            goto out;
+        if (batch == 1 || mb <= PB_DUMP_BATCH_BYTES_MAX)
+            break;
+        batch >>= 1;
+    }
+    const uint64_t cap = 24 + 16 * mf + mb + 16;
+    const size_t page = (size_t)sysconf(_SC_PAGESIZE);
+    for (int i = 0; i < 2; ++i)
+    {
+        if ((rc = pbgpu_frames_alloc(ctx, mf, mb, &src[i])) != 0 || (rc = pbgpu_frames_alloc(ctx, 1, cap, &dst[i])) != 0)
+            goto out;
+        if (posix_memalign((void **)&hb[i], page, (cap + page - 1) / page * page) != 0)
+        {
+            hb[i] = NULL;
+            rc = PBGPU_ENOMEM;
+            goto out;
+        }
+        memset(hb[i], 0, cap);
+        reg[i] = pbgpu_host_register(ctx, hb[i], cap) == 0; /* unregistered memory still works, slower */
+    }
+    const uint32_t vchecks = (seq->ip.csum ? PBGPU_VERIFY_IP_CSUM | PBGPU_VERIFY_TOT_LEN : 0u) |
+                             (seq->l4_csum ? PBGPU_VERIFY_L4_CSUM : 0u);
+    uint64_t n_cur = batch;
+    int cur = 0;
+    if ((rc = pbgpu_build(ctx, idx, 0, n_cur, src[0])) != 0)
+    {
+        fprintf(stderr, "[%d] Error building frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first, pbgpu_strerror(rc));
+        goto out;
+    }
+    while (n_cur)
+    {
+        if (D->cmd->verify)
+        {
+            pbgpu_verify_result r;
+            if ((rc = pbgpu_verify(ctx, src[cur], 0, src[cur]->n_frames, vchecks, &r, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc));
+                goto out;
+            }
+            *n_verified += src[cur]->n_frames;
+            if (r.n_bad)
+            {
+                *n_bad += r.n_bad;
+                pb_verify_failed_msg(seq_num, r.n_bad, r.first_bad, iter);
+                rc = PBGPU_EIO;
+                goto out;
+            }
+        }
+        const uint64_t have = src[cur]->n_frames;
+        const uint64_t take = have < quota - done ? have : quota - done; /* the last batch: up to the quota */
+        pbgpu_pcap_opts o;
+        memset(&o, 0, sizeof o);
+        o.t0_ns = t0_ns;
+        o.step_ps = step_ps;
+        o.first_index = done;
+        o.flags = D->header_due ? PBGPU_PCAP_FILE_HEADER : 0u;
+        uint64_t nbytes = 0;
+        if ((rc = pbgpu_pcap_pack(ctx, src[cur], 0, take, &o, dst[cur], &nbytes, NULL)) != 0)
+        {
+            fprintf(stderr, "[%d] Error packing the pcap stream on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                    pbgpu_strerror(rc));
+            goto out;
+        }
+        D->header_due = 0;
+        /* the next batch builds while this one's stream crosses the host link and is written */
+        const uint64_t left = quota - done - take;
+        uint64_t n_next = (left + fpi - 1) / fpi;
+        if (n_next > batch)
+            n_next = batch;
+        if (pb_stop_requested())
+            n_next = 0;
+        if (n_next && (rc = pbgpu_build(ctx, idx, iter + n_cur, n_next, src[cur ^ 1])) != 0)
+        {
+            fprintf(stderr, "[%d] Error building frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                    pbgpu_strerror(rc));
+            goto out;
+        }
+        if (nbytes && (rc = pbgpu_copy_packed(ctx, dst[cur], hb[cur], 0, nbytes)) != 0)
+        {
+            fprintf(stderr, "[%d] Error copying the pcap stream from GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                    pbgpu_strerror(rc));
+            goto out;
+        }
+        if (write_all(D->fd, hb[cur], nbytes) != 0)
+        {
+            fprintf(stderr, "[%d] Error writing the pcap file :: %s.\n", seq_num, strerror(errno));
+            rc = PBGPU_EIO;
+            goto out;
+        }
+        done += take;
+        iter += n_cur;
+        n_cur = n_next;
+        cur ^= 1;
+    }
+    rc = PBGPU_OK;
+out:
+    (void)pbgpu_sync(ctx);
+    for (int i = 0; i < 2; ++i)
+    {
+        if (reg[i])
+            (void)pbgpu_host_unregister(ctx, hb[i]);
+        free(hb[i]);
+        pbgpu_frames_free(ctx, dst[i]);
+        pbgpu_frames_free(ctx, src[i]);
+    }
+    *n_done = done;
+    return rc;
+}
+
+int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_xdp *cmd, const char *path, int t0_set,
+                 uint64_t t0_ns)
+{
+    int rc = pb_pcap_dump_check(cfg, seq_cnt, cmd);
+    if (rc != 0)
+        return rc;
+    if (seq_cnt > PB_MAX_SEQUENCES)
+        seq_cnt = PB_MAX_SEQUENCES;
+    if (!t0_set)
+    {
+        struct timespec ts;
+        clock_gettime(CLOCK_REALTIME, &ts);
+        t0_ns = (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+    }
+    dump_state_t D;
+    memset(&D, 0, sizeof D);
+    D.cmd = cmd;
+    D.device = cfg->interface;
+    D.header_due = 1;
+    if ((rc = pbgpu_open(cmd->gpu_first, &D.ctx)) != 0)
+    {
+        fprintf(stderr, "Error opening GPU %d :: %s.\n", cmd->gpu_first, pbgpu_strerror(rc));
+        return rc;
+    }
+    (void)pbgpu_set_timing(D.ctx, PBGPU_TIMING_SPAN); /* nobody reads per-launch timings here */
+    D.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (D.fd < 0)
+    {
+        fprintf(stderr, "Cannot open pcap file %s.\n", path);
+        pbgpu_close(D.ctx);
+        return PBGPU_EIO;
+    }
+    uint64_t verified[PB_MAX_SEQUENCES] = {0}, bad[PB_MAX_SEQUENCES] = {0};
+    time_t secs[PB_MAX_SEQUENCES] = {0};
+    int ran = 0;
+    for (int i = 0; i < seq_cnt && rc == 0 && !pb_stop_requested(); ++i)
+    {
+        const pb_sequence_t *seq = &cfg->seq[i];
+        ran = i + 1;
+        if (seq->ip.dst_ip == NULL) /* sequence.c:723-728 */
+        {
+            fprintf(stderr, "Destination IP not set on sequence #%d. Not moving forward with this sequence.\n", i + 1);
+            continue;
+        }
+        const uint64_t step_ps = seq->pps > 0 ? 1000000000000ull / seq->pps : 0;
+        uint64_t n = 0;
+        const time_t t_start = time(NULL);
+        rc = dump_sequence(&D, seq, (uint16_t)i, t0_ns, step_ps, &n, &verified[i], &bad[i]);
+        secs[i] = time(NULL) - t_start;
+        /* the next sequence continues where this one's clock stopped */
+        t0_ns += (uint64_t)((unsigned __int128)n * step_ps / 1000u);
+    }
+    if (D.header_due && rc == 0) /* nothing was packed: still a well-formed (empty) capture */
+    {
+        const uint32_t hdr[6] = {0xA1B2C3D4u, 0x00040002u, 0, 0, 65535, 1};
+        if (write_all(D.fd, (const uint8_t *)hdr, sizeof hdr) != 0)
+            rc = PBGPU_EIO;
+    }
+    if (close(D.fd) != 0 && rc == 0)
+        rc = PBGPU_EIO;
+    /* the end-of-run lines (sequence.c:779-824): the frames built and bytes stored, as the
+     * library counted them */
+    uint64_t p[PB_MAX_SEQUENCES] = {0}, b[PB_MAX_SEQUENCES] = {0};
+    const int crc = ran ? pbgpu_counters(D.ctx, p, b, ran) : 0;
+    if (crc != 0 && rc == 0)
+        rc = crc;
+    fprintf(stdout, "Completed %d sequences!\n", ran);
+    for (int i = 0; i < ran; ++i)
+        pb_print_sequence_total(i + 1, p[i], b[i], secs[i]);
+    for (int i = 0; i < ran && cmd->verify; ++i)
+        pb_print_verified(verified[i], bad[i]);
+    fflush(stdout);
+    pbgpu_close(D.ctx);
+    return rc;
+}

@@ -335,6 +335,69 @@ static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, c
             src ? src : "", sport, seq->ip.dst_ip ? seq->ip.dst_ip : "", dport);
 }
 
+/* What a sequence is loaded with, from the command line and the sequence itself: the declared
+ * rules (--literal, --singlefold) and the resolved MACs.  One place for every caller of
+ * pbgpu_load_sequence on the host side (the TX workers, the --pcapdump mode). */
+void pb_seq_prepare(const pb_sequence_t *seq, const char *device, const struct cmd_line_af_xdp *cmd, int seq_num,
+                    pb_rules_t *rules_out, uint8_t smac[6], uint8_t dmac[6])
+{
+    const pb_rules_t rules = {cmd->literal_payload ? PB_PAYLOAD_LITERAL : PB_PAYLOAD_STREAM,
+                              cmd->single_fold ? PB_FOLD_SINGLE : PB_FOLD_FULL};
+    *rules_out = rules;
+    /* MACs: a zero source MAC is the device's, a zero destination MAC the default
+     * gateway's (sequence.c:111-136) */
+    memset(smac, 0, 6);
+    memset(dmac, 0, 6);
+    if (seq->eth.src_mac)
+        sscanf(seq->eth.src_mac, "%hhx:%hhx:%hhx:%hhx:%hhx:%hhx", &smac[0], &smac[1], &smac[2], &smac[3], &smac[4],
+               &smac[5]);
+    if (seq->eth.dst_mac)
+        sscanf(seq->eth.dst_mac, "%hhx:%hhx:%hhx:%hhx:%hhx:%hhx", &dmac[0], &dmac[1], &dmac[2], &dmac[3], &dmac[4],
+               &dmac[5]);
+    static const uint8_t zero[6] = {0};
+    if (memcmp(smac, zero, 6) == 0)
+    {
+        if (device == NULL || pb_get_src_mac_address(device, smac) != 0)
+            fprintf(stdout, "[%d] WARNING - Failed to retrieve MAC address for %s.\n", seq_num,
+                    device ? device : "(no interface)");
+        if (memcmp(smac, zero, 6) == 0)
+            fprintf(stdout, "[%d] WARNING - Source MAC address retrieved is 00:00:00:00:00:00.\n", seq_num);
+    }
+    if (memcmp(dmac, zero, 6) == 0)
+        (void)pb_get_gw_mac(dmac);
+    if (verbose)
+    {
+        printf("[%d] Source MAC address => %hhx:%hhx:%hhx:%hhx:%hhx:%hhx.\n", seq_num, smac[0], smac[1], smac[2],
+               smac[3], smac[4], smac[5]);
+        printf("[%d] Destination MAC address => %hhx:%hhx:%hhx:%hhx:%hhx:%hhx.\n", seq_num, dmac[0], dmac[1], dmac[2],
+               dmac[3], dmac[4], dmac[5]);
+    }
+}
+
+void pb_verify_failed_msg(int seq_num, uint64_t bad, uint64_t first_bad, uint64_t first_iter)
+{
+    fprintf(stderr,
+            "[%d] Verify failed for sequence #%d: %llu bad frame(s), the first at frame %llu of the batch "
+            "starting at iteration %llu. Stopping the sequence.\n",
+            seq_num, seq_num, (unsigned long long)bad, (unsigned long long)first_bad, (unsigned long long)first_iter);
+}
+
+void pb_print_sequence_total(int seq_num, uint64_t p, uint64_t b, time_t secs)
+{
+    if (secs < 1)
+        secs = 1;
+    fprintf(stdout,
+            "[%d] Completed sequence with a total of %llu packets and %llu bytes. Average PPS => %llu. "
+            "Average BPS => %llu. Total seconds => %ld.\n",
+            seq_num, (unsigned long long)p, (unsigned long long)b, (unsigned long long)(p / secs),
+            (unsigned long long)(b / secs), (long)secs);
+}
+
+void pb_print_verified(uint64_t frames, uint64_t bad)
+{
+    fprintf(stdout, "Verified %llu frames on the GPU: %llu bad.\n", (unsigned long long)frames, (unsigned long long)bad);
+}
+
 static void *gpu_worker(void *p)
 {
     worker_arg_t *w = (worker_arg_t *)p;
@@ -372,34 +435,9 @@ static void *gpu_worker(void *p)
         last_error = rc;
         goto out;
     }
-    pb_rules_t rules = {w->cmd.literal_payload ? PB_PAYLOAD_LITERAL : PB_PAYLOAD_STREAM,
-                        w->cmd.single_fold ? PB_FOLD_SINGLE : PB_FOLD_FULL};
-    /* MACs: a zero source MAC is the device's, a zero destination MAC the default
-     * gateway's (sequence.c:111-136) */
-    uint8_t smac[6] = {0}, dmac[6] = {0};
-    if (seq->eth.src_mac)
-        sscanf(seq->eth.src_mac, "%hhx:%hhx:%hhx:%hhx:%hhx:%hhx", &smac[0], &smac[1], &smac[2], &smac[3], &smac[4],
-               &smac[5]);
-    if (seq->eth.dst_mac)
-        sscanf(seq->eth.dst_mac, "%hhx:%hhx:%hhx:%hhx:%hhx:%hhx", &dmac[0], &dmac[1], &dmac[2], &dmac[3], &dmac[4],
-               &dmac[5]);
-    static const uint8_t zero[6] = {0};
-    if (memcmp(smac, zero, 6) == 0)
-    {
-        if (pb_get_src_mac_address(w->device, smac) != 0)
-            fprintf(stdout, "[%d] WARNING - Failed to retrieve MAC address for %s.\n", seq_num, w->device);
-        if (memcmp(smac, zero, 6) == 0)
-            fprintf(stdout, "[%d] WARNING - Source MAC address retrieved is 00:00:00:00:00:00.\n", seq_num);
-    }
-    if (memcmp(dmac, zero, 6) == 0)
-        (void)pb_get_gw_mac(dmac);
-    if (verbose)
-    {
-        printf("[%d] Source MAC address => %hhx:%hhx:%hhx:%hhx:%hhx:%hhx.\n", seq_num, smac[0], smac[1], smac[2],
-               smac[3], smac[4], smac[5]);
-        printf("[%d] Destination MAC address => %hhx:%hhx:%hhx:%hhx:%hhx:%hhx.\n", seq_num, dmac[0], dmac[1], dmac[2],
-               dmac[3], dmac[4], dmac[5]);
-    }
+    pb_rules_t rules;
+    uint8_t smac[6], dmac[6];
+    pb_seq_prepare(seq, w->device, &w->cmd, seq_num, &rules, smac, dmac);
     if ((rc = B->load(ctx, w->seq_idx, seq, smac, dmac, &rules, w->cmd.seed_base)) != 0)
     {
         fprintf(stderr, "[%d] Error loading sequence on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
@@ -571,11 +609,8 @@ static void *gpu_worker(void *p)
             if (bad)
             {
                 __atomic_add_fetch(&verified_bad[w->seq_idx], bad, __ATOMIC_RELAXED);
-                fprintf(stderr,
-                        "[%d] Verify failed for sequence #%d: %llu bad frame(s), the first at frame %llu of the batch "
-                        "starting at iteration %llu. Stopping the sequence.\n",
-                        seq_num, seq_num, (unsigned long long)bad, (unsigned long long)first_bad,
-                        (unsigned long long)((step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch));
+                pb_verify_failed_msg(seq_num, bad, first_bad,
+                                     (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch);
                 last_error = PBGPU_EIO;
                 verify_failed[w->seq_idx] = 1;
                 break;
@@ -988,21 +1023,12 @@ int pb_shutdown_stats(pb_config_t *cfg)
             continue;
         if (end_time[i] < 1)
             end_time[i] = time(NULL);
-        time_t secs = end_time[i] - start_time[i];
-        if (secs < 1)
-            secs = 1;
-        const uint64_t p = total_pckts[i], b = total_bytes[i];
-        fprintf(stdout,
-                "[%d] Completed sequence with a total of %llu packets and %llu bytes. Average PPS => %llu. "
-                "Average BPS => %llu. Total seconds => %ld.\n",
-                i + 1, (unsigned long long)p, (unsigned long long)b, (unsigned long long)(p / secs),
-                (unsigned long long)(b / secs), (long)secs);
+        pb_print_sequence_total(i + 1, total_pckts[i], total_bytes[i], end_time[i] - start_time[i]);
     }
     /* --verify: one more line per sequence, after the reference's */
     for (int i = 0; i < seq_cnt; ++i)
         if (verify_on[i])
-            fprintf(stdout, "Verified %llu frames on the GPU: %llu bad.\n", (unsigned long long)verified_frames[i],
-                    (unsigned long long)verified_bad[i]);
+            pb_print_verified(verified_frames[i], verified_bad[i]);
     fflush(stdout);
     return last_error;
 }

@@ -24,6 +24,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <time.h>
 
 #include "../../include/pb_config.h"
 #include "../../include/pbgpu.h"
@@ -93,6 +94,18 @@ typedef struct pb_builder
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */
+
+/* ---- pieces of the worker and of the end-of-run lines shared with the --pcapdump mode
+ * (host/pcap_dump.c) ---- */
+/* What a sequence is loaded with: the declared rules (--literal, --singlefold) and the MACs, a
+ * zero source MAC resolved from `device`, a zero destination MAC from the default gateway
+ * (sequence.c:111-136), with the reference's warnings and verbose lines. */
+void pb_seq_prepare(const pb_sequence_t *seq, const char *device, const struct cmd_line_af_xdp *cmd, int seq_num,
+                    pb_rules_t *rules, uint8_t smac[6], uint8_t dmac[6]);
+/* "[n] Completed sequence with a total of ..." (sequence.c:806-820) and the --verify lines */
+void pb_print_sequence_total(int seq_num, uint64_t pckts, uint64_t bytes, time_t secs);
+void pb_print_verified(uint64_t frames, uint64_t bad);
+void pb_verify_failed_msg(int seq_num, uint64_t bad, uint64_t first_bad, uint64_t first_iter);
 
 /* pcap (LINKTYPE_ETHERNET) TX hook */
 typedef struct pb_pcap pb_pcap_t;

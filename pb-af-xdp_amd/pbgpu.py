@@ -163,6 +163,22 @@ class VerifyResult(C.Structure):
     ]
 
 
+PCAP_FILE_HEADER = 1  # the stream starts with the 24-B pcap file header
+PCAP_NSEC = 2  # nanosecond magic and ts_frac in ns (else microseconds)
+
+
+class PcapOpts(C.Structure):
+    """pbgpu_pcap_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("t0_ns", C.c_uint64),
+        ("step_ps", C.c_uint64),
+        ("first_index", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -316,6 +332,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_verify": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyResult), P]),
         "pbgpu_frames_upload": (C.c_int, [P, FP, P, U64P, C.c_uint32, C.c_uint64]),
         "pbgpu_read_probe_at": (C.c_int, [P, P, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
+        "pbgpu_pcap_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, U64P]),
+        "pbgpu_pcap_pack": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(PcapOpts), FP, U64P,
+                                      C.POINTER(C.c_double)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -413,6 +432,42 @@ class FrameBuffer:
             n, offp = len(data) // fixed_len, None
         _check(self.ctx.lib.pbgpu_frames_upload(self.ctx.h, self.ptr, data.ctypes.data if len(data) else None, offp,
                                                 fixed_len, n), "frames_upload")
+
+    def pcap_pack(self, dst: "FrameBuffer", first: int = 0, n: Optional[int] = None, t0_ns: int = 0,
+                  step_ps: int = 0, first_index: int = 0, file_header: bool = True, nsec: bool = False):
+        """Packs frames [first, first + n) (n None: to the last frame) into dst's device bytes as a
+        pcap stream: frame j stamped t0_ns + (first_index + j) * step_ps / 1000 ns.  Returns
+        (nbytes, device_ms); dst.stream(nbytes) fetches the bytes."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        opts = PcapOpts(t0_ns, step_ps, first_index,
+                        (PCAP_FILE_HEADER if file_header else 0) | (PCAP_NSEC if nsec else 0), 0)
+        nbytes, ms = C.c_uint64(), C.c_double()
+        _check(self.ctx.lib.pbgpu_pcap_pack(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(nbytes),
+                                            C.byref(ms)), "pcap_pack")
+        return int(nbytes.value), float(ms.value)
+
+    def stream(self, nbytes: int, byte_offset: int = 0) -> np.ndarray:
+        """nbytes of the buffer's device bytes from byte_offset (a packed pcap stream's window)."""
+        out = np.empty(nbytes, dtype=np.uint8)
+        if nbytes:
+            _check(self.ctx.lib.pbgpu_copy_packed(self.ctx.h, self.ptr, out.ctypes.data, byte_offset, nbytes),
+                   "copy_packed")
+        return out
+
+    def pcap_bytes(self, first: int = 0, n: Optional[int] = None, t0_ns: int = 0, step_ps: int = 0,
+                   first_index: int = 0, file_header: bool = True, nsec: bool = False) -> np.ndarray:
+        """The pcap stream of frames [first, first + n) as host bytes: allocates a buffer of the
+        stream's size, packs into it, copies back and frees it."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        flags = (PCAP_FILE_HEADER if file_header else 0) | (PCAP_NSEC if nsec else 0)
+        dst = self.ctx.alloc_frames(1, max(16, self.ctx.pcap_size(self, first, n, flags)))
+        try:
+            nbytes, _ = self.pcap_pack(dst, first, n, t0_ns, step_ps, first_index, file_header, nsec)
+            return dst.stream(nbytes)
+        finally:
+            dst.free()
 
     def free(self) -> None:
         if self.ptr is not None:
@@ -529,6 +584,14 @@ class GpuContext:
         ms = C.c_double()
         _check(self.lib.pbgpu_read_probe_at(self.h, fb.f.data, nbytes, reps, C.byref(ms)), "read_probe_at")
         return float(ms.value)
+
+    def pcap_size(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, flags: int = PCAP_FILE_HEADER) -> int:
+        """Bytes of the pcap stream of fb's frames [first, first + n) (n None: to the last frame)."""
+        if n is None:
+            n = int(fb.f.n_frames) - first
+        nbytes = C.c_uint64()
+        _check(self.lib.pbgpu_pcap_size(self.h, fb.ptr, first, n, flags, C.byref(nbytes)), "pcap_size")
+        return int(nbytes.value)
 
     def kernel_name(self, idx: int) -> str:
         buf = C.create_string_buffer(96)
