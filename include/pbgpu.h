@@ -228,6 +228,57 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
                     const pbgpu_pcap_opts *opts, pbgpu_frames *dst,
                     uint64_t *nbytes, double *device_ms /* may be NULL */);
 
+/* ---- encapsulation: built (or uploaded) frames repacked with an 802.1Q tag or a VXLAN outer
+ * header on the device ---- */
+#define PBGPU_ENCAP_VLAN  1u
+#define PBGPU_ENCAP_VXLAN 2u
+typedef struct pbgpu_encap_opts {
+    uint32_t mode;         /* PBGPU_ENCAP_VLAN or PBGPU_ENCAP_VXLAN; anything else: -EINVAL        */
+    uint32_t flags;        /* must be 0                                                            */
+    /* VLAN */
+    uint16_t tpid;         /* 0 -> 0x8100                                                          */
+    uint16_t tci;          /* PCP << 13 | DEI << 12 | VID                                          */
+    /* VXLAN (RFC 7348) */
+    uint16_t src_port;     /* outer UDP source port; 0 -> hashed from the inner frame, see below   */
+    uint16_t dst_port;     /* 0 -> 4789                                                            */
+    uint32_t vni;          /* < 2^24                                                               */
+    uint8_t dst_mac[6];    /* outer addresses, wire order                                          */
+    uint8_t src_mac[6];
+    uint8_t src_ip[4];
+    uint8_t dst_ip[4];
+    uint8_t ttl;           /* 0 -> 64                                                              */
+    uint8_t tos;
+    uint16_t reserved;     /* must be 0                                                            */
+} pbgpu_encap_opts;
+
+/* Output frame j of frames [first_frame, first_frame + n) of `src`, L the source frame's length:
+ *   VLAN  (P = 4):  src[0:12] + BE16(tpid) + BE16(tci) + src[12:L]
+ *   VXLAN (P = 50): dst_mac, src_mac, 08 00;
+ *                   45, tos, BE16(L + 36), 00 00, 40 00, ttl, 11, csum, src_ip, dst_ip   (csum: RFC 1071)
+ *                   BE16(sport), BE16(dst_port), BE16(L + 16), 00 00                     (UDP checksum 0)
+ *                   08 00 00 00, vni as 3 bytes big-endian, 00;  then src[0:L]
+ *     sport = src_port, or for src_port == 0: source bytes 26..37 (a missing byte counts as 0) as three
+ *     little-endian u32 w0 w1 w2; x = w0^w1^w2; x ^= x >> 16; x *= 0x7FEB352D (mod 2^32); x ^= x >> 15;
+ *     sport = 49152 + (x & 0x3FFF).
+ * pbgpu_encap_size gives the output's frame count (n) and bytes (the frames' bytes + n * P).
+ * pbgpu_encap writes the frames packed from byte 0 of dst->data, zeros up to the next multiple of 16
+ * and nothing past that.  dst is then a frames buffer as after an upload: n_frames = n, fixed_len =
+ * src->fixed_len + P (0 for a variable-length source), total_bytes, and for variable length the device
+ * offsets[j] = off(first_frame + j) - off(first_frame) + j * P, j in [0, n]; pbgpu_verify, the landing
+ * calls, pbgpu_pcap_pack and another pbgpu_encap take it like any built buffer.  src is only read.
+ * Runs on the context's stream after the build or upload of src and after earlier work on dst and
+ * the landings queued from it; returns when the frames are in place.  n == 0: dst becomes empty,
+ * nothing is written.  pbgpu_counters is unchanged.
+ * -EINVAL: NULL arguments, src never built or uploaded, a range past src->n_frames, src == dst or
+ * overlapping data, unknown mode, flags or reserved nonzero, vni >= 2^24, src's shortest frame below
+ * 14 B or its longest above 65535 - P (a buffer's shortest and longest frame are recorded by its build
+ * or upload).  -ENOSPC: dst->capacity_frames < n or dst->capacity_bytes below the output rounded up
+ * to 16.  On any error dst is unchanged. */
+int pbgpu_encap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                     const pbgpu_encap_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                const pbgpu_encap_opts *opts, pbgpu_frames *dst, double *device_ms /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -280,7 +331,7 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  * which: 0 sizeof(pb_sequence_t), 1 sizeof(pb_payload_opt_t), 2 sizeof(pbgpu_frames),
  *        3 offsetof(pb_sequence_t, ip.ranges), 4 offsetof(pb_sequence_t, pls),
  *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
- *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts);
+ *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

@@ -259,6 +259,33 @@ struct pb_pcargs
     uint64_t t0_ns, step_ps, first_index;
 };
 
+// ---- encapsulation (pbgpu_encap: pb_encap_kernel) ----
+// Output record j = source frame first + j with P header bytes inserted `split` bytes in.
+#define PB_EN_WT 256u                // threads per workgroup: one 16-B chunk each, a 4-KiB page of the output per step
+#define PB_EN_WIN (PB_EN_WT + 2u)    // variable length: record positions kept in LDS (a page touches at most 229 records of >= 18 B)
+#define PB_EN_HREC 232u              // header slots per page (>= 229 records and the one after)
+#define PB_EN_TDW 13u                // template dwords: P <= 52
+#define PB_EN_HDW (PB_EN_TDW + 1u)   // a staged header, moved to its destination's alignment: up to P + 3 bytes
+#define PB_EN_HASH 1u                // pb_enargs.flags: the outer UDP source port is hashed from source bytes 26..37
+#define PB_EN_VXLAN 2u               // patch tot_len, the IPv4 checksum and the UDP length per record (variable length)
+struct pb_enargs
+{
+    const uint8_t *src;      // src->data (16-B aligned)
+    const uint64_t *offsets; // src->offsets (variable length), null for fixed length
+    uint8_t *dst;            // dst->data (16-B aligned)
+    uint64_t *dst_offsets;   // dst->offsets (variable length)
+    uint64_t first, n;       // frames [first, first + n)
+    uint64_t end16;          // output bytes rounded up to 16: what is written
+    uint32_t fixed_len;
+    pb_div rec;              // fixed length: the record size fixed_len + P
+    uint32_t P, split;       // header bytes, and where in the frame they go
+    uint32_t hdw;            // dwords per staged header: (P + 3) / 4 + 1
+    uint32_t flags;
+    uint32_t per;            // pages per workgroup
+    uint32_t csum_base;      // VXLAN: the IPv4 header's 16-bit words summed with tot_len and the checksum 0
+    uint32_t tpl[PB_EN_TDW]; // the header bytes, little-endian dwords, zero padded (fixed length: lengths and checksum filled in)
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

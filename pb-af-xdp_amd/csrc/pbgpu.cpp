@@ -49,6 +49,7 @@ extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t g
 extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -259,6 +260,9 @@ struct frames_events
     // pbgpu_frames_upload, variable length: the longest uploaded frame + 1 (what a landing checks
     // against its slot, in place of the building sequence's longest frame); 0 after a build
     uint32_t up_max_len1 = 0;
+    // the buffer's shortest and longest frame: the building sequence's, or the uploaded frames'
+    // (pbgpu_encap refuses frames it cannot encapsulate); both 0 while the buffer holds no frames
+    uint32_t min_len = 0, max_len = 0;
 };
 
 frames_events *frames_ev(pbgpu_frames *f)
@@ -1824,6 +1828,8 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
     fe->last = st;
     fe->packed32 = false;
     fe->up_max_len1 = 0;
+    fe->min_len = S.min_flen;
+    fe->max_len = S.max_flen;
     // a landing queued from this buffer must have read it before the build overwrites it
     if (fe->land_pending)
     {
@@ -2390,7 +2396,7 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
 {
     if (ctx == NULL || f == NULL)
         return PBGPU_EINVAL;
-    uint64_t total = 0, max_len = 0;
+    uint64_t total = 0, max_len = 0, min_len = UINT64_MAX;
     if (host_offsets)
     {
         for (uint64_t i = 0; i < n; ++i)
@@ -2398,6 +2404,7 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
             if (host_offsets[i + 1] < host_offsets[i] || host_offsets[i + 1] - host_offsets[i] > PB_MAX_PCKT_LEN)
                 return PBGPU_EINVAL;
             max_len = host_offsets[i + 1] - host_offsets[i] > max_len ? host_offsets[i + 1] - host_offsets[i] : max_len;
+            min_len = host_offsets[i + 1] - host_offsets[i] < min_len ? host_offsets[i + 1] - host_offsets[i] : min_len;
         }
         total = host_offsets[n] - host_offsets[0];
         fixed_len = 0;
@@ -2407,7 +2414,10 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
         if (fixed_len == 0 || fixed_len > PB_MAX_PCKT_LEN)
             return PBGPU_EINVAL;
         total = n * fixed_len;
+        min_len = max_len = fixed_len;
     }
+    if (n == 0)
+        min_len = max_len = 0;
     if (total && host_data == NULL)
         return PBGPU_EINVAL;
     if (n > f->capacity_frames || n > 0xFFFFFFFFull || ((total + 15) & ~15ull) > f->capacity_bytes)
@@ -2429,6 +2439,8 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
     fe->last = st;
     fe->packed32 = false;
     fe->up_max_len1 = host_offsets ? (uint32_t)max_len + 1 : 0;
+    fe->min_len = (uint32_t)min_len;
+    fe->max_len = (uint32_t)max_len;
     if (fe->land_pending)
     {
         HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
@@ -2594,6 +2606,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
     fe->last = st;
     fe->packed32 = false;
     fe->up_max_len1 = 0;
+    fe->min_len = fe->max_len = 0;
     if (fe->land_pending)
     {
         HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
@@ -2649,6 +2662,184 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
     if (device_ms)
         *device_ms = ms;
     return PBGPU_OK;
+}
+
+// ---- encapsulation ----
+
+// Argument checks shared by pbgpu_encap_size and pbgpu_encap, then the header's size and the
+// frames' bytes (pcap_body).
+static int encap_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_encap_opts *opts,
+                       uint32_t *P, uint64_t *body, uint64_t *src_end)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || src->reserved == NULL)
+        return PBGPU_EINVAL;
+    if (opts->mode != PBGPU_ENCAP_VLAN && opts->mode != PBGPU_ENCAP_VXLAN)
+        return PBGPU_EINVAL;
+    if (opts->flags != 0 || opts->reserved != 0 || opts->vni >= (1u << 24))
+        return PBGPU_EINVAL;
+    *P = opts->mode == PBGPU_ENCAP_VLAN ? 4u : 50u;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (src->n_frames && (fs->min_len < 14u || fs->max_len > 65535u - *P))
+        return PBGPU_EINVAL;
+    return pcap_body(ctx, src, first, n, 0, body, src_end);
+}
+
+int pbgpu_encap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                     const pbgpu_encap_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    uint32_t P = 0;
+    uint64_t body = 0, src_end = 0;
+    const int rc = encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end);
+    if (rc != PBGPU_OK)
+        return rc;
+    *frames = n;
+    *bytes = body + n * P;
+    return PBGPU_OK;
+}
+
+int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_encap_opts *opts,
+                pbgpu_frames *dst, double *device_ms)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
+        return PBGPU_EINVAL;
+    if (src == dst || src->data == NULL || dst->data == NULL)
+        return PBGPU_EINVAL;
+    {
+        // the allocations, the readers' 64-B slack included
+        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
+        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
+        if (s0 < d1 && d0 < s1)
+            return PBGPU_EINVAL;
+    }
+    uint32_t P = 0;
+    uint64_t body = 0, src_end = 0;
+    const int brc = encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end);
+    if (brc != PBGPU_OK)
+        return brc;
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    const uint64_t total = body + n * P;
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (n > dst->capacity_frames || end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    frames_events *fe = frames_ev(dst);
+    if (fe == NULL)
+        return PBGPU_ENOMEM;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const uint32_t src_min = fs->min_len, src_max = fs->max_len;
+    // as an upload: after dst's last build on another stream and the landings queued from it
+    hipStream_t st = ctx->stream;
+    if (fe->last && fe->last != st)
+    {
+        if (fe->moved == nullptr)
+            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fe->moved, fe->last));
+        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
+    }
+    fe->last = st;
+    fe->packed32 = false;
+    fe->up_max_len1 = (n && !src->fixed_len) ? src_max + P + 1 : 0;
+    fe->min_len = n ? src_min + P : 0;
+    fe->max_len = n ? src_max + P : 0;
+    if (fe->land_pending)
+    {
+        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
+        fe->land_pending = false;
+    }
+    float ms = 0;
+    if (n)
+    {
+        pb_enargs A;
+        memset(&A, 0, sizeof A);
+        A.src = src->data;
+        A.offsets = src->fixed_len ? nullptr : src->offsets;
+        A.dst = dst->data;
+        A.dst_offsets = dst->offsets;
+        A.first = first_frame;
+        A.n = n;
+        A.end16 = end16;
+        A.fixed_len = src->fixed_len;
+        A.rec = make_div(src->fixed_len + P);
+        A.P = P;
+        A.hdw = (P + 6u) / 4u; // P + 3 bytes in dwords
+        uint8_t t[PB_EN_TDW * 4];
+        memset(t, 0, sizeof t);
+        if (opts->mode == PBGPU_ENCAP_VLAN)
+        {
+            const uint16_t tpid = opts->tpid ? opts->tpid : 0x8100;
+            A.split = 12;
+            t[0] = (uint8_t)(tpid >> 8), t[1] = (uint8_t)tpid;
+            t[2] = (uint8_t)(opts->tci >> 8), t[3] = (uint8_t)opts->tci;
+        }
+        else
+        {
+            const uint16_t dport = opts->dst_port ? opts->dst_port : 4789;
+            A.split = 0;
+            A.flags = PB_EN_VXLAN | (opts->src_port ? 0u : PB_EN_HASH);
+            memcpy(t, opts->dst_mac, 6);
+            memcpy(t + 6, opts->src_mac, 6);
+            t[12] = 0x08;
+            t[14] = 0x45, t[15] = opts->tos;
+            t[20] = 0x40; // DF
+            t[22] = opts->ttl ? opts->ttl : 64, t[23] = 17;
+            memcpy(t + 26, opts->src_ip, 4);
+            memcpy(t + 30, opts->dst_ip, 4);
+            t[34] = (uint8_t)(opts->src_port >> 8), t[35] = (uint8_t)opts->src_port;
+            t[36] = (uint8_t)(dport >> 8), t[37] = (uint8_t)dport;
+            t[42] = 0x08;
+            t[46] = (uint8_t)(opts->vni >> 16), t[47] = (uint8_t)(opts->vni >> 8), t[48] = (uint8_t)opts->vni;
+            for (int i = 14; i < 34; i += 2)
+                A.csum_base += ((uint32_t)t[i] << 8) | t[i + 1];
+            if (src->fixed_len) // the same for every frame: only a hashed source port is left to the device
+            {
+                const uint32_t tot = src->fixed_len + 36u, ulen = src->fixed_len + 16u;
+                uint32_t c = A.csum_base + tot;
+                while (c >> 16)
+                    c = (c & 0xFFFFu) + (c >> 16);
+                c = ~c & 0xFFFFu;
+                t[16] = (uint8_t)(tot >> 8), t[17] = (uint8_t)tot;
+                t[24] = (uint8_t)(c >> 8), t[25] = (uint8_t)c;
+                t[38] = (uint8_t)(ulen >> 8), t[39] = (uint8_t)ulen;
+            }
+        }
+        for (uint32_t i = 0; i < PB_EN_TDW; ++i)
+            A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
+                       ((uint32_t)t[4 * i + 3] << 24);
+        // pages per workgroup as pbgpu_pcap_pack: at least 16384 workgroups in a large launch, and a
+        // grid below 2^24 however long the output
+        const uint64_t npages = (end16 + 4095) >> 12;
+        uint64_t per = npages / 16384;
+        per = per < 1 ? 1 : (per > 32 ? 32 : per);
+        if ((npages + per - 1) / per > (1ull << 24))
+            per = (npages + (1ull << 24) - 1) >> 24;
+        if (per > 0xFFFFFFFFull)
+            return PBGPU_EINVAL;
+        A.per = (uint32_t)per;
+        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        timing_pair tp;
+        {
+            const int prc = timed_pair(ctx, &tp);
+            if (prc != PBGPU_OK)
+                return prc;
+        }
+        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
+        HIPCHK(hipEventRecord(tp.a, st));
+        HIPCHK(pbk_launch_encap(&A, grid, st)); // variable length: dst->offsets by a launch of its own first
+        HIPCHK(hipEventRecord(tp.b, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = n;
+    dst->fixed_len = src->fixed_len ? src->fixed_len + P : 0;
+    dst->total_bytes = total;
+    if (device_ms)
+        *device_ms = ms;
+    return mark_built(ctx, dst, st);
 }
 
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
@@ -3197,6 +3388,7 @@ size_t pbgpu_abi_size(int which)
     case 6: return offsetof(pbgpu_frames, total_bytes);
     case 7: return sizeof(pbgpu_verify_result);
     case 8: return sizeof(pbgpu_pcap_opts);
+    case 9: return sizeof(pbgpu_encap_opts);
     default: return 0;
     }
 }

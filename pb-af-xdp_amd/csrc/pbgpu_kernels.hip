@@ -4554,3 +4554,316 @@ extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStre
         hipLaunchKernelGGL((pb_pcap_kernel<false>), dim3(grid), dim3(PB_PC_WT), 0, st, *A);
     return hipGetLastError();
 }
+
+// ---------------- encapsulation (pbgpu_encap) ----------------
+// Output record j is source frame first + j with P header bytes inserted `split` bytes in, so the
+// output is the source byte stream with n insertions: between header j and header j + 1 every
+// byte sits at its source position + (j + 1) P.  Destination-owned as pb_pcap_kernel: a workgroup
+// owns `per` consecutive 4-KiB pages of the output, a lane one aligned 16-B chunk of a page per
+// step.  Per page, one lane per record touching the page first stages that record's header in
+// LDS, its per-frame fields filled in and its bytes moved to the alignment they have in the
+// output, so that an aligned destination dword needs exactly one staged dword.  After a barrier
+// every chunk is one sequence: the source stream at the two shifts a chunk can see (a record is
+// at least 18 B: a chunk holds bytes of at most two records), a staged dword of each of the two
+// headers, and three byte masks per dword that select among them.  A wave none of whose chunks
+// touches a header takes a plain shifted copy instead; the choice is per wave, never per lane.
+
+// bytes b of the dword at offset o with o + b < bound, as a byte mask
+__device__ __forceinline__ uint32_t pb_en_lt(int32_t o, int32_t bound)
+{
+    const int32_t k = bound - o;
+    return k <= 0 ? 0u : (k >= 4 ? 0xFFFFFFFFu : (1u << (8u * (uint32_t)k)) - 1u);
+}
+
+// source bytes [a, a + 16) as four dwords, of which bytes [lo, hi) of the 16 are wanted (the rest
+// unspecified): aligned dwords, loaded only if they hold a wanted byte, moved by v_alignbyte
+__device__ __forceinline__ void pb_en_gather(const uint32_t *w, int64_t a, int32_t lo, int32_t hi, uint32_t out[4])
+{
+    const int64_t i = a >> 2; // floor: a is negative only where nothing before byte 0 is wanted
+    const uint32_t sh = (uint32_t)a & 3u;
+    uint32_t d[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+    {
+        const int32_t b = 4 * t - (int32_t)sh; // the dword's first byte among the 16
+        d[t] = (b + 4 > lo && b < hi) ? w[i + t] : 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        out[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
+}
+
+// the last k in [0, PB_EN_WIN) with s_rel[k] <= d
+__device__ __forceinline__ uint32_t pb_en_find(const uint32_t *s_rel, uint32_t d)
+{
+    uint32_t lo = 0, hi = PB_EN_WIN - 1u;
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (s_rel[mid] <= d)
+            lo = mid;
+        else
+            hi = mid - 1u;
+    }
+    return lo;
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
+{
+    // variable length: output positions of PB_EN_WIN records from record j0 on, relative to it
+    // (below 258 * 65535); 0xFFFFFFFF past the end of the range
+    __shared__ uint32_t s_rel[PB_EN_WIN];
+    // slot i: the header of the i-th record touching the page, A.hdw dwords
+    __shared__ uint32_t s_hdr[PB_EN_HREC * PB_EN_HDW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+    const uint32_t P = A.P, hdw = A.hdw;
+    const int32_t S = (int32_t)A.split;
+    const uint32_t reclen = A.fixed_len + P;
+    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
+    if (p >= A.end16)
+        return;
+    // j0: the record holding the first page's first byte, d0: that byte's offset in the record
+    uint64_t j0 = 0, g0 = 0;
+    const uint64_t ob = VAR ? A.offsets[A.first] : 0;
+    if (p > 0)
+    {
+        if (VAR)
+        {
+            // P j + offsets[first + j] rises with j: the last j in [0, n] at or below p
+            uint64_t lo = 0, hi = A.n;
+            while (lo < hi)
+            {
+                const uint64_t mid = lo + (hi - lo + 1) / 2;
+                if ((uint64_t)P * mid + (A.offsets[A.first + mid] - ob) <= p)
+                    lo = mid;
+                else
+                    hi = mid - 1;
+            }
+            j0 = lo;
+            g0 = (uint64_t)P * lo + (A.offsets[A.first + lo] - ob);
+        }
+        else
+        {
+            j0 = p / reclen; // the one 64-bit division, once per workgroup
+            g0 = j0 * reclen;
+        }
+    }
+    int32_t d0 = (int32_t)(p - g0);
+    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
+    bool have_win = false;
+    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    {
+        // variable length: the window is kept from page to page (d0 then grows by 4096 a page) and
+        // moved to the record holding the page's first byte only when it no longer reaches the
+        // record after the page's last byte
+        uint32_t kw = 0; // the window's index of the record holding the page's first byte
+        if (VAR)
+        {
+            if (!have_win || (int64_t)s_rel[PB_EN_WIN - 1u] <= (int64_t)d0 + 4095)
+            {
+                if (have_win)
+                {
+                    const uint32_t lo = pb_en_find(s_rel, (uint32_t)d0);
+                    j0 += lo;
+                    d0 -= (int32_t)s_rel[lo];
+                }
+                __syncthreads(); // the window's readers are done
+                offj0 = A.offsets[A.first + (j0 < A.n ? j0 : A.n)];
+                for (uint32_t k = tid; k < PB_EN_WIN; k += PB_EN_WT)
+                {
+                    const uint64_t jj = j0 + k;
+                    s_rel[k] = jj <= A.n ? P * k + (uint32_t)(A.offsets[A.first + jj] - offj0) : 0xFFFFFFFFu;
+                }
+                have_win = true;
+            }
+            __syncthreads(); // the window is in place, the last page's header readers are done
+            kw = pb_en_find(s_rel, (uint32_t)d0);
+        }
+        else
+            __syncthreads(); // the last page's header readers are done
+        const uint64_t fj0 = VAR ? 0 : (A.first + j0) * A.fixed_len; // fixed length: frame first + j0's offset in src
+
+        // ---- header stage: lane i stages the header of the i-th record touching the page ----
+        if (tid < PB_EN_HREC)
+        {
+            const uint32_t k = kw + tid;
+            bool act;
+            uint32_t rs = 0, rlen = reclen; // the record's start relative to record j0, its length
+            if (VAR)
+            {
+                act = k + 1u < PB_EN_WIN;
+                if (act)
+                {
+                    rs = s_rel[k];
+                    const uint32_t re = s_rel[k + 1u];
+                    act = re != 0xFFFFFFFFu; // entries j0 + k and j0 + k + 1 are at most n
+                    rlen = re - rs;
+                }
+            }
+            else
+            {
+                rs = k * reclen;
+                act = j0 + k < A.n;
+            }
+            if (act && (int64_t)rs < (int64_t)d0 + 4096)
+            {
+                const uint32_t L = rlen - P;
+                uint32_t T[PB_EN_TDW + 1u];
+#pragma unroll
+                for (uint32_t u = 0; u < PB_EN_TDW; ++u)
+                    T[u] = A.tpl[u];
+                T[PB_EN_TDW] = 0u;
+                if (VAR && (A.flags & PB_EN_VXLAN))
+                {
+                    // tot_len (bytes 16-17), the IPv4 checksum (24-25: the constant words + tot_len,
+                    // folded) and the UDP length (38-39)
+                    const uint32_t tot = L + 36u;
+                    const uint32_t c = ~pb_fold(A.csum_base + tot) & 0xFFFFu;
+                    T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
+                    T[6] = (T[6] & 0xFFFF0000u) | pb_bswap16(c);
+                    T[9] = (T[9] & 0x0000FFFFu) | (pb_bswap16(L + 16u) << 16);
+                }
+                if (A.flags & PB_EN_HASH)
+                {
+                    // source bytes 26..37 as aligned dwords; bytes past the frame count as 0
+                    const uint64_t so = VAR ? offj0 + (rs - P * k) : fj0 + (uint64_t)k * A.fixed_len;
+                    const uint64_t a = so + 26u, end = so + L;
+                    const uint64_t i = a >> 2;
+                    const uint32_t sh = (uint32_t)a & 3u;
+                    uint32_t d[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
+                    const int32_t vb = (int32_t)L - 26; // bytes of the twelve inside the frame
+                    uint32_t x = 0;
+#pragma unroll
+                    for (int t = 0; t < 3; ++t)
+                        x ^= __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh) & pb_en_lt(4 * t, vb);
+                    x ^= x >> 16;
+                    x *= 0x7FEB352Du;
+                    x ^= x >> 15;
+                    const uint32_t sport = 49152u + (x & 0x3FFFu);
+                    T[8] = (T[8] & 0x0000FFFFu) | (pb_bswap16(sport) << 16); // bytes 34-35
+                }
+                // moved to the output's alignment: staged dword u is output bytes hb + 4u .. + 3,
+                // hb the header's first byte rounded down to 4
+                const int32_t hs = (int32_t)rs + S - d0; // the header's first byte in the page (below 0: before it)
+                const uint32_t sh = (uint32_t)hs & 3u;
+                uint32_t *slot = s_hdr + tid * hdw;
+#pragma unroll
+                for (uint32_t u = 0; u < PB_EN_HDW; ++u)
+                    if (u < hdw)
+                        slot[u] = sh ? __builtin_amdgcn_alignbyte(T[u], u ? T[u - 1u] : 0u, 4u - sh) : T[u];
+            }
+        }
+        __syncthreads();
+
+        // ---- chunks ----
+        const int32_t d = d0 + 16 * (int32_t)tid;
+        const uint64_t pc = p + 16u * tid;
+        if (pc < A.end16)
+        {
+            // k, r: the chunk starts r bytes into record j0 + k, which is ea bytes long; pc is
+            // below the output's last byte, so that record is inside the range
+            uint32_t k, rs, ea;
+            if (VAR)
+            {
+                k = pb_en_find(s_rel, (uint32_t)d);
+                rs = s_rel[k];
+                ea = s_rel[k + 1u] - rs;
+            }
+            else
+            {
+                k = pb_divq((uint32_t)d, A.rec);
+                rs = k * reclen;
+                ea = reclen;
+            }
+            const int32_t r = d - (int32_t)rs;
+            const bool bvalid = j0 + k + 1u < A.n; // a next record: its first bytes may end the chunk
+            const int64_t offa = (int64_t)(VAR ? offj0 + (rs - P * k) : fj0 + (uint64_t)k * A.fixed_len);
+            // the record's bytes: [0, S) source, [S, S + P) header, [S + P, e3) source P bytes back
+            // (through the next record's first S bytes: frames are packed), from e3 the next header
+            // or, past the range, zeros
+            const int32_t sp = S + (int32_t)P;
+            const int32_t e3 = bvalid ? (int32_t)ea + S : (int32_t)ea;
+            pb_u32x4 v;
+            // A wave whose chunks all lie wholly in source bytes behind their record's header (two waves
+            // of three at 1500 B) copies: four aligned dwords and, off alignment, a fifth, which still
+            // holds a byte of the frame.  Decided per wave, so no lane waits for another's path.
+            if (__ballot(!(r >= sp && r + 16 <= e3)) == 0ull)
+            {
+                const uint64_t a = (uint64_t)(offa + r - (int32_t)P); // at or after the frame's byte S
+                const uint64_t i = a >> 2;
+                const uint32_t sh = (uint32_t)a & 3u;
+                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
+                const uint32_t w4 = sh ? w[i + 4] : 0u;
+                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
+                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
+                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+            }
+            else
+            {
+                uint32_t s0[4] = {0u, 0u, 0u, 0u}, s1[4];
+                {
+                    const int32_t lo = (r > sp ? r : sp) - r;
+                    const int32_t hi = (r + 16 < e3 ? r + 16 : e3) - r;
+                    pb_en_gather(w, offa + r - (int32_t)P, lo, hi, s1);
+                }
+                if (S)
+                    pb_en_gather(w, offa + r, 0, S - r, s0);
+                const uint32_t ia = k - kw; // the record's header slot; the next record's is the one after
+                const int32_t hsa = (int32_t)rs + S - d0, hsb = hsa + (int32_t)ea;
+                const int32_t q = 16 * (int32_t)tid;
+                const int32_t ua = (q - (hsa & ~3)) >> 2, ub = (q - (hsb & ~3)) >> 2;
+                uint32_t o4[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                {
+                    const uint32_t va = (uint32_t)(ua + t) < hdw ? s_hdr[ia * hdw + (uint32_t)(ua + t)] : 0u;
+                    const uint32_t vb =
+                        bvalid && (uint32_t)(ub + t) < hdw ? s_hdr[(ia + 1u) * hdw + (uint32_t)(ub + t)] : 0u;
+                    const int32_t o = r + 4 * t;
+                    const uint32_t m1 = pb_en_lt(o, S), m2 = pb_en_lt(o, sp), m3 = pb_en_lt(o, e3);
+                    o4[t] = (s0[t] & m1) | (va & m2 & ~m1) | (s1[t] & m3 & ~m2) | (vb & ~m3);
+                }
+                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+            }
+            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
+        }
+        // the next page's first byte: 4096 on in the same window, or a whole number of records on
+        if (VAR)
+            d0 += 4096;
+        else
+        {
+            const int32_t dn = d0 + 4096;
+            const uint32_t kn = pb_divq((uint32_t)dn, A.rec);
+            d0 = dn - (int32_t)(kn * reclen);
+            j0 += kn;
+        }
+    }
+}
+
+// dst->offsets of a variable-length encapsulation: entry j = off(first + j) - off(first) + j P, j in [0, n]
+__global__ __launch_bounds__(256) void pb_encap_offsets_kernel(const uint64_t *offsets, uint64_t first, uint64_t n,
+                                                               uint32_t P, uint64_t *out)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j <= n)
+        out[j] = offsets[first + j] - offsets[first] + j * P;
+}
+
+extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st)
+{
+    if (A->offsets)
+    {
+        hipLaunchKernelGGL(pb_encap_offsets_kernel, dim3((uint32_t)((A->n + 256u) / 256u)), dim3(256), 0, st,
+                           A->offsets, A->first, A->n, A->P, A->dst_offsets);
+        hipLaunchKernelGGL((pb_encap_kernel<true>), dim3(grid), dim3(PB_EN_WT), 0, st, *A);
+    }
+    else
+        hipLaunchKernelGGL((pb_encap_kernel<false>), dim3(grid), dim3(PB_EN_WT), 0, st, *A);
+    return hipGetLastError();
+}

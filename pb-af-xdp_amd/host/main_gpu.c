@@ -13,6 +13,7 @@
  * otherwise the in-memory ring of host/xsk_ring.c, whose consumer writes a pcap
  * file with --pcap (or only counts).
  */
+#include <arpa/inet.h>
 #include <getopt.h>
 #include <signal.h>
 #include <stdio.h>
@@ -37,6 +38,9 @@ static pb_config_t *cfg;
 static const char *pcapdump_path;
 static int pcapt0_set;
 static uint64_t pcapt0_ns;
+/* --encap vlan:VID[:PCP] | vxlan:VNI:SRCIP:DSTIP[:DPORT], once: handed to the driver with pb_set_encap */
+static const char *encap_spec;
+static int encap_twice;
 
 static void sign_hdl(int sig)
 {
@@ -49,7 +53,7 @@ enum
     O_INTERFACE = 256, O_BLOCK, O_TRACK, O_MAXPCKTS, O_MAXBYTES, O_PPS, O_BPS, O_DELAY, O_THREADS, O_L4CSUM, O_SMAC,
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
-    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0,
+    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP,
 };
 
 static const struct option common_opts[] = {
@@ -89,6 +93,7 @@ static const struct option common_opts[] = {
     {"umemframes", required_argument, NULL, O_SECOND_PASS}, {"umemslot", required_argument, NULL, O_SECOND_PASS},
     {"verify", no_argument, NULL, O_SECOND_PASS},
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
+    {"encap", required_argument, NULL, O_ENCAP},
     {NULL, 0, NULL, 0},
 };
 
@@ -173,9 +178,112 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
         case O_TIME: s->time = strtoull(a, NULL, 10); break;
         case O_PCAPDUMP: pcapdump_path = a; break;
         case O_PCAPT0: pcapt0_ns = strtoull(a, NULL, 10); pcapt0_set = 1; break;
+        case O_ENCAP: /* the -z pass reads the same argument again */
+            if (encap_spec && encap_spec != a)
+                encap_twice = 1;
+            encap_spec = a;
+            break;
         default: break;
         }
     }
+}
+
+/* a decimal number in [0, max] filling the whole field */
+static int field_u32(const char *s, uint32_t max, uint32_t *out)
+{
+    if (s == NULL || *s < '0' || *s > '9')
+        return -1;
+    char *end = NULL;
+    const unsigned long long v = strtoull(s, &end, 10);
+    if (*end != '\0' || v > max)
+        return -1;
+    *out = (uint32_t)v;
+    return 0;
+}
+
+/* --encap's argument -> the options the driver completes with each sequence's MACs; -1 and a
+ * message in `why` for a malformed one */
+static int parse_encap(const char *spec, pbgpu_encap_opts *o, const char **why)
+{
+    char buf[128];
+    char *f[6] = {NULL};
+    int nf = 0;
+    memset(o, 0, sizeof *o);
+    if (strlen(spec) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    strcpy(buf, spec);
+    for (char *p = buf; nf < 6; ++nf)
+    {
+        f[nf] = p;
+        p = strchr(p, ':');
+        if (p == NULL)
+        {
+            ++nf;
+            break;
+        }
+        *p++ = '\0';
+    }
+    uint32_t v = 0;
+    if (strcmp(f[0], "vlan") == 0)
+    {
+        o->mode = PBGPU_ENCAP_VLAN;
+        if (nf < 2 || nf > 3)
+        {
+            *why = "expected vlan:VID[:PCP]";
+            return -1;
+        }
+        if (field_u32(f[1], 4095, &v) != 0)
+        {
+            *why = "VID is 0-4095";
+            return -1;
+        }
+        o->tci = (uint16_t)v;
+        if (nf == 3)
+        {
+            if (field_u32(f[2], 7, &v) != 0)
+            {
+                *why = "PCP is 0-7";
+                return -1;
+            }
+            o->tci |= (uint16_t)(v << 13);
+        }
+        return 0;
+    }
+    if (strcmp(f[0], "vxlan") == 0)
+    {
+        o->mode = PBGPU_ENCAP_VXLAN;
+        if (nf < 4 || nf > 5)
+        {
+            *why = "expected vxlan:VNI:SRCIP:DSTIP[:DPORT]";
+            return -1;
+        }
+        if (field_u32(f[1], (1u << 24) - 1, &v) != 0)
+        {
+            *why = "VNI is 0-16777215";
+            return -1;
+        }
+        o->vni = v;
+        if (inet_pton(AF_INET, f[2], o->src_ip) != 1 || inet_pton(AF_INET, f[3], o->dst_ip) != 1)
+        {
+            *why = "SRCIP and DSTIP are dotted IPv4 addresses";
+            return -1;
+        }
+        if (nf == 5)
+        {
+            if (field_u32(f[4], 65535, &v) != 0 || v == 0)
+            {
+                *why = "DPORT is 1-65535";
+                return -1;
+            }
+            o->dst_port = (uint16_t)v;
+        }
+        return 0;
+    }
+    *why = "expected vlan:... or vxlan:...";
+    return -1;
 }
 
 static void print_cmd_help(void)
@@ -188,11 +296,14 @@ static void print_cmd_help(void)
                     "-z --cli => Enables the first sequence/packet override (README.md first-sequence options).\n\n"
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
-                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS\n"
+                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC\n"
                     "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
                     "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
                     "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
-                    "1/pps per frame.\n");
+                    "1/pps per frame.\n"
+                    "--encap vlan:VID[:PCP] | vxlan:VNI:SRCIP:DSTIP[:DPORT] => Encapsulate every frame on the GPU before "
+                    "it is sent or dumped: an 802.1Q tag, or a VXLAN outer header (the sequence's MACs, TTL 64, source "
+                    "port hashed from the inner frame, DPORT 4789 by default).\n");
 }
 
 int main(int argc, char **argv)
@@ -222,6 +333,22 @@ int main(int argc, char **argv)
     {
         print_cmd_help();
         return EXIT_SUCCESS;
+    }
+    if (encap_spec) /* refused before anything else is set up */
+    {
+        pbgpu_encap_opts eo;
+        const char *why = NULL;
+        if (encap_twice)
+        {
+            fprintf(stderr, "--encap given more than once: one encapsulation per run.\n");
+            return EXIT_FAILURE;
+        }
+        if (parse_encap(encap_spec, &eo, &why) != 0)
+        {
+            fprintf(stderr, "--encap %s: %s.\n", encap_spec, why);
+            return EXIT_FAILURE;
+        }
+        pb_set_encap(&eo);
     }
     struct cmd_line_af_xdp cmd_af_xdp = {0};
     cmd_line_af_xdp_defaults(&cmd_af_xdp);

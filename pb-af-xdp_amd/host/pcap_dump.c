@@ -2,7 +2,7 @@
  * pcap_dump.c — pcktbatch-gpu --pcapdump (pcap_dump.h).
  *
  * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
- * Batch k is (verified,) packed into stream buffer k & 1; batch k + 1's build is queued into the
+ * Batch k is (verified, with --encap encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
  * other frame buffer; then stream k is copied to its host buffer in one piece and written with
  * one write() per buffer (looped only on a short write).
  */
@@ -86,6 +86,7 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
     const int seq_num = idx + 1;
     pbgpu_ctx *ctx = D->ctx;
     pbgpu_frames *src[2] = {NULL, NULL}, *dst[2] = {NULL, NULL};
+    pbgpu_frames *enc = NULL; /* --encap: the batch as it is packed (the pack returns before the next encap) */
     uint8_t *hb[2] = {NULL, NULL};
     int reg[2] = {0, 0};
     int rc;
@@ -98,6 +99,15 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         fprintf(stderr, "[%d] Error loading sequence on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first, pbgpu_strerror(rc));
         return rc;
     }
+    /* --encap: the outer MACs are the sequence's */
+    const int encap = pb_get_encap() != NULL;
+    pbgpu_encap_opts eopts;
+    memset(&eopts, 0, sizeof eopts);
+    if (encap)
+        eopts = *pb_get_encap();
+    memcpy(eopts.dst_mac, dmac, 6);
+    memcpy(eopts.src_mac, smac, 6);
+    const uint32_t extra = encap ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u;
     const uint32_t fpi = seq->pl_cnt < 1 ? 1u : seq->pl_cnt;
     const uint64_t quota = seq->max_pckts;
     uint64_t batch = D->cmd->gpu_batch ? D->cmd->gpu_batch : (1u << 20);
@@ -112,7 +122,9 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
             break;
         batch >>= 1;
     }
-    const uint64_t cap = 24 + 16 * mf + mb + 16;
+    const uint64_t cap = 24 + (16 + extra) * mf + mb + 16;
+    if (encap && (rc = pbgpu_frames_alloc(ctx, mf, mb + extra * mf + 16, &enc)) != 0)
+        goto out;
     const size_t page = (size_t)sysconf(_SC_PAGESIZE);
     for (int i = 0; i < 2; ++i)
     {
@@ -158,6 +170,12 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         }
         const uint64_t have = src[cur]->n_frames;
         const uint64_t take = have < quota - done ? have : quota - done; /* the last batch: up to the quota */
+        if (encap && (rc = pbgpu_encap(ctx, src[cur], 0, take, &eopts, enc, NULL)) != 0)
+        {
+            fprintf(stderr, "[%d] Error encapsulating frames on GPU %d :: %s%s.\n", seq_num, D->cmd->gpu_first,
+                    pbgpu_strerror(rc), rc == PBGPU_EINVAL ? " (a frame too long for the outer header?)" : "");
+            goto out;
+        }
         pbgpu_pcap_opts o;
         memset(&o, 0, sizeof o);
         o.t0_ns = t0_ns;
@@ -165,7 +183,7 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         o.first_index = done;
         o.flags = D->header_due ? PBGPU_PCAP_FILE_HEADER : 0u;
         uint64_t nbytes = 0;
-        if ((rc = pbgpu_pcap_pack(ctx, src[cur], 0, take, &o, dst[cur], &nbytes, NULL)) != 0)
+        if ((rc = pbgpu_pcap_pack(ctx, encap ? enc : src[cur], 0, take, &o, dst[cur], &nbytes, NULL)) != 0)
         {
             fprintf(stderr, "[%d] Error packing the pcap stream on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
                     pbgpu_strerror(rc));
@@ -213,6 +231,7 @@ out:
         pbgpu_frames_free(ctx, dst[i]);
         pbgpu_frames_free(ctx, src[i]);
     }
+    pbgpu_frames_free(ctx, enc);
     *n_done = done;
     return rc;
 }
@@ -249,7 +268,7 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         pbgpu_close(D.ctx);
         return PBGPU_EIO;
     }
-    uint64_t verified[PB_MAX_SEQUENCES] = {0}, bad[PB_MAX_SEQUENCES] = {0};
+    uint64_t verified[PB_MAX_SEQUENCES] = {0}, bad[PB_MAX_SEQUENCES] = {0}, written[PB_MAX_SEQUENCES] = {0};
     time_t secs[PB_MAX_SEQUENCES] = {0};
     int ran = 0;
     for (int i = 0; i < seq_cnt && rc == 0 && !pb_stop_requested(); ++i)
@@ -268,6 +287,7 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         secs[i] = time(NULL) - t_start;
         /* the next sequence continues where this one's clock stopped */
         t0_ns += (uint64_t)((unsigned __int128)n * step_ps / 1000u);
+        written[i] = n;
     }
     if (D.header_due && rc == 0) /* nothing was packed: still a well-formed (empty) capture */
     {
@@ -284,6 +304,10 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
     if (crc != 0 && rc == 0)
         rc = crc;
     fprintf(stdout, "Completed %d sequences!\n", ran);
+    /* --encap: the library counts the frames as built; the file holds the header bytes as well */
+    if (pb_get_encap())
+        for (int i = 0; i < ran; ++i)
+            b[i] += written[i] * (pb_get_encap()->mode == PBGPU_ENCAP_VLAN ? 4u : 50u);
     for (int i = 0; i < ran; ++i)
         pb_print_sequence_total(i + 1, p[i], b[i], secs[i]);
     for (int i = 0; i < ran && cmd->verify; ++i)

@@ -58,6 +58,8 @@ static int verbose;
 static pb_tx_fn tx_hook;
 static void *tx_ctx;
 static volatile int stop_requested;
+static int encap_on; /* --encap (pb_set_encap) */
+static pbgpu_encap_opts encap_opts;
 
 void pb_request_stop(void)
 {
@@ -78,6 +80,18 @@ void pb_set_tx_hook(pb_tx_fn fn, void *ctx)
 void pb_set_verbose(int v)
 {
     verbose = v;
+}
+
+void pb_set_encap(const pbgpu_encap_opts *opts)
+{
+    encap_on = opts != NULL;
+    if (opts)
+        encap_opts = *opts;
+}
+
+const pbgpu_encap_opts *pb_get_encap(void)
+{
+    return encap_on ? &encap_opts : NULL;
 }
 
 int pb_last_error(void)
@@ -176,6 +190,23 @@ static int gb_verify(void *h, void *frames, uint32_t checks, uint64_t *n_bad, ui
         *n_bad = r.n_bad, *first_bad = r.first_bad;
     return rc;
 }
+static int gb_alloc_encap(void *h, uint16_t i, uint64_t n_iter, uint32_t extra, void **frames, uint32_t *max_len)
+{
+    /* 16 iterations: the size bound is then the frames times the sequence's longest frame, plus 16 */
+    uint64_t mf = 0, mb = 0;
+    int rc = pbgpu_build_size((pbgpu_ctx *)h, i, 16, &mf, &mb);
+    if (rc != 0 || mf == 0)
+        return rc ? rc : PBGPU_EINVAL;
+    *max_len = (uint32_t)((mb - 16) / mf);
+    if ((rc = pbgpu_build_size((pbgpu_ctx *)h, i, n_iter, &mf, &mb)) == 0)
+        rc = pbgpu_frames_alloc((pbgpu_ctx *)h, mf, mb + mf * extra + 16, (pbgpu_frames **)frames);
+    return rc;
+}
+static int gb_encap(void *h, void *src, const pbgpu_encap_opts *opts, void *dst)
+{
+    pbgpu_frames *f = (pbgpu_frames *)src;
+    return pbgpu_encap((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -187,7 +218,7 @@ static void gb_close(void *h)
 
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
-                                         gb_verify};
+                                         gb_verify, gb_alloc_encap, gb_encap};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -311,12 +342,23 @@ static void tx_sink(void *ctx, const uint8_t *frame, uint32_t len, uint64_t addr
  * UMEM slot: "[seq][payload] Sent <len> bytes of data from <src>:<sport> to <dst>:<dport>."
  * The source is the configured src_ip string, else the frame's drawn source address (rand_ip's
  * dotted string); the ports are the UDP / TCP header's (0 for ICMP), the destination the
- * configured dst_ip string. */
+ * configured dst_ip string.  Under --encap vlan the one 802.1Q tag (ethertype 0x8100 at byte 12) is
+ * skipped; under --encap vxlan the line reports the outer addresses and ports: what is sent. */
 static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, const uint8_t *fr, uint16_t len)
 {
-    char sip[16];
+    char sip[16], dip[16];
     const char *src = seq->ip.src_ip;
+    const char *dst = seq->ip.dst_ip;
     uint32_t sport = 0, dport = 0;
+    const uint16_t wire_len = len;
+    if (encap_on && encap_opts.mode == PBGPU_ENCAP_VXLAN && len >= 34)
+    {
+        src = NULL;
+        snprintf(dip, sizeof dip, "%u.%u.%u.%u", fr[30], fr[31], fr[32], fr[33]);
+        dst = dip;
+    }
+    if (len >= 18 && fr[12] == 0x81 && fr[13] == 0x00) /* one 802.1Q tag (--encap vlan): the addresses behind it */
+        fr += 4, len -= 4;
     if (len >= 34)
     {
         if (src == NULL)
@@ -331,8 +373,8 @@ static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, c
             dport = ((uint32_t)fr[l4 + 2] << 8) | fr[l4 + 3];
         }
     }
-    fprintf(stdout, "[%d][%u] Sent %u bytes of data from %s:%u to %s:%u.\n", seq_num, pl_idx + 1, (unsigned)len,
-            src ? src : "", sport, seq->ip.dst_ip ? seq->ip.dst_ip : "", dport);
+    fprintf(stdout, "[%d][%u] Sent %u bytes of data from %s:%u to %s:%u.\n", seq_num, pl_idx + 1, (unsigned)wire_len,
+            src ? src : "", sport, dst ? dst : "", dport);
 }
 
 /* What a sequence is loaded with, from the command line and the sequence itself: the declared
@@ -406,6 +448,7 @@ static void *gpu_worker(void *p)
     const pb_builder_t *B = builder;
     void *ctx = NULL;
     void *fr[2] = {NULL, NULL};
+    void *efr[2] = {NULL, NULL}; /* --encap: what is landed */
     uint8_t *umem = NULL;
     int registered = 0;
     pb_xsk_t xsk;
@@ -448,6 +491,13 @@ static void *gpu_worker(void *p)
     uint32_t max_flen = 42 + 12; /* headers */
     for (uint16_t i = 0; i < seq->pl_cnt; ++i)
         max_flen += seq->pls[i].max_len > 0 ? seq->pls[i].max_len : 1024; /* static lengths are bounded by the parser */
+    /* --encap: the outer MACs are the sequence's */
+    const int enc = encap_on;
+    pbgpu_encap_opts eopts = encap_opts;
+    const uint32_t enc_extra = enc ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u;
+    memcpy(eopts.dst_mac, dmac, 6);
+    memcpy(eopts.src_mac, smac, 6);
+    max_flen += enc_extra;
     uint64_t batch = w->cmd.gpu_batch ? w->cmd.gpu_batch : (1u << 20);
     while (batch > 1 && batch * fpi * max_flen > PB_BATCH_BYTES_MAX)
         batch >>= 1;
@@ -487,6 +537,24 @@ static void *gpu_worker(void *p)
     {
         last_error = rc;
         goto out;
+    }
+    if (enc)
+    {
+        uint32_t longest = 0;
+        if ((rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[0], &longest)) != 0 ||
+            (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[1], &longest)) != 0)
+        {
+            last_error = rc;
+            goto out;
+        }
+        const uint32_t slot = w->cmd.umem_slot ? w->cmd.umem_slot : PB_FRAME_SIZE;
+        if (longest + enc_extra > slot || longest + enc_extra > 65535u)
+        {
+            fprintf(stderr, "[%d] --encap: the sequence's longest frame (%u B) plus %u B does not fit a %u-B UMEM slot.\n",
+                    seq_num, longest, enc_extra, slot < 65535u ? slot : 65535u);
+            last_error = PBGPU_EINVAL;
+            goto out;
+        }
     }
     uint8_t *umem_base = NULL; /* the UMEM the TX ring addresses (shared: the sequence's) */
     if (w->shared)
@@ -616,6 +684,38 @@ static void *gpu_worker(void *p)
                 break;
             }
         }
+        if (enc)
+        {
+            if ((rc = B->encap(ctx, fr[cur], &eopts, efr[cur])) != 0)
+            {
+                fprintf(stderr, "[%d] Error encapsulating frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+            /* the outer header is Ethernet + IPv4 + UDP with a zero UDP checksum (RFC 7348): its IPv4
+             * checksum and length are checked; a VLAN frame is not one the verifier parses */
+            if (w->cmd.verify && eopts.mode == PBGPU_ENCAP_VXLAN)
+            {
+                uint64_t bad = 0, first_bad = 0;
+                if ((rc = B->verify(ctx, efr[cur], PBGPU_VERIFY_IP_CSUM | PBGPU_VERIFY_TOT_LEN, &bad, &first_bad)) != 0)
+                {
+                    fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, w->gpu,
+                            pbgpu_strerror(rc));
+                    last_error = rc;
+                    break;
+                }
+                if (bad)
+                {
+                    __atomic_add_fetch(&verified_bad[w->seq_idx], bad, __ATOMIC_RELAXED);
+                    pb_verify_failed_msg(seq_num, bad, first_bad,
+                                         (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch);
+                    last_error = PBGPU_EIO;
+                    verify_failed[w->seq_idx] = 1;
+                    break;
+                }
+            }
+        }
+        void *const lf = enc ? efr[cur] : fr[cur]; /* what lands: its lengths are what the ring and the totals count */
         /* double buffering: the next batch builds on the GPU while this one lands */
         const uint64_t n_next = claim_iters(w->seq_idx, seq->max_pckts, batch, fpi);
         if (n_next &&
@@ -626,7 +726,7 @@ static void *gpu_worker(void *p)
             last_error = rc;
             break;
         }
-        const uint64_t nf = B->n_frames(fr[cur]);
+        const uint64_t nf = B->n_frames(lf);
         /* land in slot-ring order with up to PB_LAND_INFLIGHT landings queued: chunk
          * c + 1 lands while chunk c is submitted (their latencies overlap) */
         uint64_t f0 = 0, f_issue = 0;
@@ -653,7 +753,7 @@ static void *gpu_worker(void *p)
                     n = (uint32_t)(nf - f_issue);
                 if (n > nslots - land_slot) /* the slot ring wraps: a chunk never does */
                     n = nslots - land_slot;
-                if ((rc = B->land(ctx, fr[cur], umem, slot_sz, land_slot, f_issue, n, lens + land_slot)) != 0)
+                if ((rc = B->land(ctx, lf, umem, slot_sz, land_slot, f_issue, n, lens + land_slot)) != 0)
                 {
                     fprintf(stderr, "[%d] Error landing frames from GPU %d :: %s%s.\n", seq_num, w->gpu,
                             pbgpu_strerror(rc),
@@ -854,8 +954,12 @@ out:
     if (w->shared)
         shared_release(w->shared);
     for (int i = 0; i < 2; ++i)
+    {
         if (fr[i])
             B->free_frames(ctx, fr[i]);
+        if (efr[i])
+            B->free_frames(ctx, efr[i]);
+    }
     if (ctx)
         B->close(ctx);
     free(lens);
@@ -895,6 +999,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
             last_error = PBGPU_ENODEV;
             return;
         }
+    }
+    if (encap_on && (builder->encap == NULL || builder->alloc_encap == NULL))
+    {
+        fprintf(stderr, "[%d] --encap: this frame builder cannot encapsulate.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
     }
     if (cmd.umem_slot && (cmd.umem_slot < 64 || cmd.umem_slot > PB_FRAME_SIZE || (cmd.umem_slot & (cmd.umem_slot - 1)) ||
                           (uint64_t)(cmd.umem_frames ? cmd.umem_frames : PB_NUM_FRAMES) * (PB_FRAME_SIZE / cmd.umem_slot) >

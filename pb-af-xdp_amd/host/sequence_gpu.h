@@ -42,6 +42,12 @@ void pb_set_tx_hook(pb_tx_fn fn, void *tx_ctx);
 void pb_request_stop(void); /* async-signal-safe: workers stop after their current batch */
 int pb_stop_requested(void);
 void pb_set_verbose(int verbose);
+/* --encap (main_gpu.c's own option, like --pcapdump): every sequence's frames are encapsulated on
+ * the GPU (pbgpu_encap) before they are landed or packed.  The mode and its fields as parsed; the
+ * outer MACs are filled in per sequence from the ones pb_seq_prepare resolves, TTL 64, TOS 0, the
+ * source port hashed.  NULL: none (the default). */
+void pb_set_encap(const pbgpu_encap_opts *opts);
+const pbgpu_encap_opts *pb_get_encap(void);
 
 void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cmd_line_af_xdp cmd);
 /* sequence.c:779-824: stop and join the workers, print the end-of-run lines,
@@ -91,6 +97,11 @@ typedef struct pb_builder
     /* --verify: the batch in `frames` checked where it was built (pbgpu_verify with `checks`): the
      * bad frames and the first one's index.  NULL: --verify is refused. */
     int (*verify)(void *h, void *frames, uint32_t checks, uint64_t *n_bad, uint64_t *first_bad);
+    /* --encap: a buffer for n_iter iterations' frames with `extra` more bytes each, and the sequence's
+     * longest frame; the built batch `src` encapsulated into such a buffer (pbgpu_encap), which then
+     * lands and verifies like a built one.  NULL: --encap is refused. */
+    int (*alloc_encap)(void *h, uint16_t seq_idx, uint64_t n_iter, uint32_t extra, void **frames, uint32_t *max_len);
+    int (*encap)(void *h, void *src, const pbgpu_encap_opts *opts, void *dst);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

@@ -179,6 +179,44 @@ class PcapOpts(C.Structure):
     ]
 
 
+ENCAP_VLAN = 1  # an 802.1Q tag after the MAC addresses (4 B)
+ENCAP_VXLAN = 2  # outer Ethernet + IPv4 + UDP + VXLAN in front of the frame (50 B, RFC 7348)
+
+
+class EncapOpts(C.Structure):
+    """pbgpu_encap_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("tpid", C.c_uint16),
+        ("tci", C.c_uint16),
+        ("src_port", C.c_uint16),
+        ("dst_port", C.c_uint16),
+        ("vni", C.c_uint32),
+        ("dst_mac", C.c_uint8 * 6),
+        ("src_mac", C.c_uint8 * 6),
+        ("src_ip", C.c_uint8 * 4),
+        ("dst_ip", C.c_uint8 * 4),
+        ("ttl", C.c_uint8),
+        ("tos", C.c_uint8),
+        ("reserved", C.c_uint16),
+    ]
+
+    @classmethod
+    def make(cls, mode: int, **fields) -> "EncapOpts":
+        """mode and any of the struct's fields; addresses as bytes in wire order."""
+        o = cls()
+        o.mode = mode
+        for k, v in fields.items():
+            if k in ("dst_mac", "src_mac", "src_ip", "dst_ip"):
+                v = type(getattr(o, k)).from_buffer_copy(bytes(v))
+            elif k not in dict(cls._fields_):
+                raise TypeError(f"EncapOpts has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -335,6 +373,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_pcap_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, U64P]),
         "pbgpu_pcap_pack": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(PcapOpts), FP, U64P,
                                       C.POINTER(C.c_double)]),
+        "pbgpu_encap_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(EncapOpts), U64P, U64P]),
+        "pbgpu_encap": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(EncapOpts), FP, C.POINTER(C.c_double)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -469,6 +509,19 @@ class FrameBuffer:
         finally:
             dst.free()
 
+    def encap(self, dst: "FrameBuffer", first: int = 0, n: Optional[int] = None, mode: int = ENCAP_VLAN,
+              opts: Optional[EncapOpts] = None, **fields) -> float:
+        """Encapsulates frames [first, first + n) (n None: to the last frame) into dst, which is then
+        a frames buffer like a built one: mode ENCAP_VLAN (tci, tpid) or ENCAP_VXLAN (dst_mac, src_mac,
+        src_ip, dst_ip, vni, src_port, dst_port, ttl, tos), or a ready EncapOpts.  Returns device ms."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        if opts is None:
+            opts = EncapOpts.make(mode, **fields)
+        ms = C.c_double()
+        _check(self.ctx.lib.pbgpu_encap(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(ms)), "encap")
+        return float(ms.value)
+
     def free(self) -> None:
         if self.ptr is not None:
             self.ctx.lib.pbgpu_frames_free(self.ctx.h, self.ptr)
@@ -592,6 +645,15 @@ class GpuContext:
         nbytes = C.c_uint64()
         _check(self.lib.pbgpu_pcap_size(self.h, fb.ptr, first, n, flags, C.byref(nbytes)), "pcap_size")
         return int(nbytes.value)
+
+    def encap_size(self, fb: "FrameBuffer", first: int, n: Optional[int], opts: EncapOpts):
+        """(frames, bytes) of the encapsulation of fb's frames [first, first + n) (n None: to the last frame)."""
+        if n is None:
+            n = int(fb.f.n_frames) - first
+        frames, nbytes = C.c_uint64(), C.c_uint64()
+        _check(self.lib.pbgpu_encap_size(self.h, fb.ptr, first, n, C.byref(opts), C.byref(frames), C.byref(nbytes)),
+               "encap_size")
+        return int(frames.value), int(nbytes.value)
 
     def kernel_name(self, idx: int) -> str:
         buf = C.create_string_buffer(96)
