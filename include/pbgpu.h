@@ -279,6 +279,58 @@ int pbgpu_encap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, ui
 int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                 const pbgpu_encap_opts *opts, pbgpu_frames *dst, double *device_ms /* may be NULL */);
 
+/* ---- IPv4 fragmentation: built (or uploaded) frames repacked so that no IPv4 packet exceeds an
+ * MTU, on the device ---- */
+#define PBGPU_FRAG_IGNORE_DF 1u
+typedef struct pbgpu_frag_opts {
+    uint32_t mtu;      /* largest IPv4 packet (tot_len) allowed, 68..65535; else -EINVAL */
+    uint32_t flags;    /* PBGPU_FRAG_IGNORE_DF; any other bit: -EINVAL */
+    uint64_t reserved; /* must be 0 */
+} pbgpu_frag_opts;
+typedef struct pbgpu_frag_result {
+    uint64_t n_in, n_out;      /* source frames taken, frames written */
+    uint64_t n_split;          /* source frames written as 2 or more fragments */
+    uint64_t n_df;             /* oversize, DF set, copied whole (no IGNORE_DF) */
+    uint64_t n_other;          /* oversize but not Ethernet + IPv4 without options, copied whole */
+    uint64_t out_bytes;
+    uint32_t out_min_len, out_max_len;
+    double   device_ms;        /* all launches of the call, one event pair */
+} pbgpu_frag_result;
+
+/* For a source frame of length L: fo = BE16 of bytes 20..21, C = (mtu - 20) & ~7, D = L - 34.
+ * The frame is copied as one output frame, unchanged, when L < 34, bytes 12..13 are not 08 00, byte
+ * 14 is not 0x45, L - 14 <= mtu (the frame length decides, not the stored tot_len, as in
+ * pbgpu_verify), or fo & 0x4000 is set and IGNORE_DF is not.  Otherwise it becomes K = ceil(D / C)
+ * output frames: fragment i carries source bytes 34 + iC .. 34 + min(D, (i + 1) C) behind src[0:14]
+ * and the source's 20 header bytes with tot_len = 20 + its data bytes, the fragment field =
+ * (fo & 0xC000) | MF | (((fo & 0x1FFF) + iC / 8) & 0x1FFF), MF = 0x2000 for i < K - 1 and fo & 0x2000
+ * for the last, and the header checksum recomputed (RFC 1071); a source that is itself a fragment
+ * is so split correctly.
+ * pbgpu_fragment writes the output frames packed from byte 0 of dst->data in source and fragment
+ * order, zeros up to the next multiple of 16 and nothing past that.  dst is then a frames buffer as
+ * after an upload: n_frames = n_out, fixed_len = 0 with the device offsets[0 .. n_out] written
+ * (fixed_len = src->fixed_len for a fixed-length source with src->fixed_len - 14 <= mtu, none of
+ * whose frames can split), total_bytes, and the exact shortest and longest output frame recorded;
+ * pbgpu_verify, the landing calls, pbgpu_pcap_pack, pbgpu_encap and another pbgpu_fragment take it
+ * like any built buffer.  src is only read; pbgpu_counters is unchanged.  Runs on the context's
+ * stream after the build or upload of src and after earlier work on dst and the landings queued
+ * from it; returns when the frames are in place.  n == 0: dst becomes empty.
+ * pbgpu_fragment_size gives the exact output frame count and bytes (the count and scan passes
+ * only).  pbgpu_fragment_bound answers from src's recorded longest frame with no device work: with
+ * Kmax = max(1, ceil((max_len - 34) / C)), frames <= n * Kmax and bytes <= n * max_len +
+ * 34 n (Kmax - 1) for a variable-length source (the range's exact bytes + 34 n (Kmax - 1) for a
+ * fixed-length one).
+ * -EINVAL: NULL arguments, src never built or uploaded, a range past src->n_frames, src == dst or
+ * overlapping data, mtu outside 68..65535, unknown flag bits, reserved != 0, src's shortest frame
+ * below 14 B.  -ENOSPC: dst->capacity_frames < n_out or dst->capacity_bytes below the output rounded
+ * up to 16.  On any error dst is unchanged. */
+int pbgpu_fragment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                        const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_fragment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                         const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                   const pbgpu_frag_opts *opts, pbgpu_frames *dst, pbgpu_frag_result *res /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -331,7 +383,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  * which: 0 sizeof(pb_sequence_t), 1 sizeof(pb_payload_opt_t), 2 sizeof(pbgpu_frames),
  *        3 offsetof(pb_sequence_t, ip.ranges), 4 offsetof(pb_sequence_t, pls),
  *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
- *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts);
+ *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts),
+ *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

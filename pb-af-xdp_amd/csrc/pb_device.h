@@ -286,6 +286,39 @@ struct pb_enargs
     uint32_t tpl[PB_EN_TDW]; // the header bytes, little-endian dwords, zero padded (fixed length: lengths and checksum filled in)
 };
 
+// ---- IPv4 fragmentation (pbgpu_fragment: pb_frag_*_kernel) ----
+// Output record f = fragment i of source frame first + j (or the whole frame, copied).
+#define PB_FG_WT 256u                // threads per workgroup: one source frame each (count, map), one 16-B chunk each (writer)
+#define PB_FG_CB 16u                 // count: rows of PB_FG_WT frames per workgroup
+#define PB_FG_WIN 320u               // writer: record positions kept in LDS (a page touches at most 294 records of >= 14 B, and one entry ends the last)
+#define PB_FG_HREC 300u              // header slots per page
+#define PB_FG_HDW 10u                // a staged 34-B header, moved to its destination's alignment: up to 37 bytes
+#define PB_FG_IGNORE_DF 1u           // pb_fgargs.flags, as PBGPU_FRAG_IGNORE_DF
+// map entry of an output record: the source frame's byte offset in src (48 bits), then
+#define PB_FG_M_ISH 48u              // ... the fragment index i (11 bits)
+#define PB_FG_M_SPLIT (1u << 11)     // ... (entry >> 48) bit: the record is a fragment (its header is staged and patched)
+#define PB_FG_M_LAST (1u << 12)      // ... the frame's last fragment (MF as the source has it)
+#define PB_FG_RES_DW 8u              // result words: n_out, n_split, n_df, n_other, min len, max len
+struct pb_fgargs
+{
+    const uint8_t *src;      // src->data (16-B aligned)
+    const uint64_t *offsets; // src->offsets (variable length), null for fixed length
+    uint8_t *dst;            // dst->data (16-B aligned)
+    uint64_t *dst_offsets;   // dst->offsets
+    uint64_t first, n;       // source frames [first, first + n)
+    uint64_t n_out;          // output records (writer, map)
+    uint64_t total, end16;   // output bytes, and rounded up to 16: what is written
+    uint32_t fixed_len;
+    uint32_t mtu, C;         // C = (mtu - 20) & ~7: data bytes of a full fragment
+    pb_div cdiv;             // division by C
+    uint32_t flags;
+    uint32_t per;            // writer: pages per workgroup
+    uint32_t *kcnt;          // K per source frame of the range
+    unsigned long long *bsum; // K summed per count workgroup, then their exclusive scan
+    unsigned long long *res; // PB_FG_RES_DW words
+    uint64_t *map;           // n_out entries
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

@@ -50,6 +50,7 @@ extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsig
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -300,6 +301,12 @@ struct pbgpu_ctx
     unsigned long long *h_vres = nullptr, *d_vres = nullptr;
     uint8_t *d_vcodes = nullptr;
     uint64_t vcodes_cap = 0;
+    // pbgpu_fragment: the count pass's scratch (result words, workgroup sums, K per source frame)
+    // and the map (one entry per output record), each grown on demand
+    uint8_t *d_fg_cnt = nullptr;
+    uint64_t fg_cnt_cap = 0; // source frames
+    uint64_t *d_fg_map = nullptr;
+    uint64_t fg_map_cap = 0; // output records
     seq_slot seqs[PB_MAX_SEQUENCES];
     std::vector<timing_pair> pending;
     std::vector<timing_pair> pool;
@@ -821,6 +828,10 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipHostFree(ctx->h_vres);
     if (ctx->d_vcodes)
         (void)hipFree(ctx->d_vcodes);
+    if (ctx->d_fg_cnt)
+        (void)hipFree(ctx->d_fg_cnt);
+    if (ctx->d_fg_map)
+        (void)hipFree(ctx->d_fg_map);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->d_lens)
@@ -2842,6 +2853,243 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
     return mark_built(ctx, dst, st);
 }
 
+// ---- IPv4 fragmentation ----
+
+// Argument checks shared by the three calls; nothing on the device.
+static int frag_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || src->reserved == NULL)
+        return PBGPU_EINVAL;
+    if (opts->mtu < 68u || opts->mtu > 65535u || (opts->flags & ~PBGPU_FRAG_IGNORE_DF) || opts->reserved != 0)
+        return PBGPU_EINVAL;
+    if (first > src->n_frames || n > src->n_frames - first)
+        return PBGPU_EINVAL;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (src->n_frames && fs->min_len < 14u)
+        return PBGPU_EINVAL;
+    return PBGPU_OK;
+}
+
+static void frag_args(pb_fgargs *A, const pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts)
+{
+    memset(A, 0, sizeof *A);
+    A->src = src->data;
+    A->offsets = src->fixed_len ? nullptr : src->offsets;
+    A->first = first;
+    A->n = n;
+    A->fixed_len = src->fixed_len;
+    A->mtu = opts->mtu;
+    A->C = (opts->mtu - 20u) & ~7u;
+    A->cdiv = make_div(A->C);
+    A->flags = (opts->flags & PBGPU_FRAG_IGNORE_DF) ? PB_FG_IGNORE_DF : 0u;
+}
+
+// The count and scan stages, queued on the context's stream: A's scratch pointers are set, the
+// result words arrive in res[] with the stream's next synchronise.
+static int frag_count(pbgpu_ctx *ctx, pb_fgargs *A, unsigned long long *res)
+{
+    const uint64_t nblk = (A->n + PB_FG_WT - 1u) / PB_FG_WT;
+    if (nblk > 0xFFFFFFFFull)
+        return PBGPU_EINVAL;
+    if (A->n > ctx->fg_cnt_cap)
+    {
+        if (ctx->d_fg_cnt)
+            (void)hipFree(ctx->d_fg_cnt);
+        ctx->d_fg_cnt = nullptr;
+        ctx->fg_cnt_cap = 0;
+        if (hipMalloc((void **)&ctx->d_fg_cnt, PB_FG_RES_DW * 8u + nblk * 8u + A->n * 4u) != hipSuccess)
+            return PBGPU_ENOMEM;
+        ctx->fg_cnt_cap = A->n;
+    }
+    A->res = (unsigned long long *)ctx->d_fg_cnt;
+    A->bsum = A->res + PB_FG_RES_DW;
+    A->kcnt = (uint32_t *)(A->bsum + nblk);
+    HIPCHK(pbk_launch_frag(A, 0, 0, ctx->stream));
+    HIPCHK(hipMemcpyAsync(res, A->res, PB_FG_RES_DW * 8u, hipMemcpyDeviceToHost, ctx->stream));
+    return PBGPU_OK;
+}
+
+int pbgpu_fragment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                         const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    const int rc = frag_check(ctx, src, first_frame, n, opts);
+    if (rc != PBGPU_OK)
+        return rc;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const uint64_t C = (opts->mtu - 20u) & ~7u, max_len = fs->max_len;
+    uint64_t kmax = 1;
+    if (max_len > opts->mtu + 14ull)
+        kmax = (max_len - 34u + C - 1u) / C;
+    *frames = n * kmax;
+    *bytes = n * (src->fixed_len ? src->fixed_len : max_len) + 34u * n * (kmax - 1u);
+    return PBGPU_OK;
+}
+
+int pbgpu_fragment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                        const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    const int rc = frag_check(ctx, src, first_frame, n, opts);
+    if (rc != PBGPU_OK)
+        return rc;
+    uint64_t body = 0, src_end = 0;
+    const int brc = pcap_body(ctx, src, first_frame, n, 0, &body, &src_end);
+    if (brc != PBGPU_OK)
+        return brc;
+    *frames = n;
+    *bytes = body;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (n == 0 || fs->max_len <= opts->mtu + 14u) // nothing can split
+        return PBGPU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    pb_fgargs A;
+    frag_args(&A, src, first_frame, n, opts);
+    unsigned long long r[PB_FG_RES_DW];
+    const int crc = frag_count(ctx, &A, r);
+    if (crc != PBGPU_OK)
+        return crc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (r[0] < n)
+        return PBGPU_EIO;
+    *frames = r[0];
+    *bytes = body + 34u * (r[0] - n);
+    return PBGPU_OK;
+}
+
+int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_frag_opts *opts,
+                   pbgpu_frames *dst, pbgpu_frag_result *res)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
+        return PBGPU_EINVAL;
+    if (src == dst || src->data == NULL || dst->data == NULL)
+        return PBGPU_EINVAL;
+    {
+        // the allocations, the readers' 64-B slack included
+        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
+        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
+        if (s0 < d1 && d0 < s1)
+            return PBGPU_EINVAL;
+    }
+    const int rc = frag_check(ctx, src, first_frame, n, opts);
+    if (rc != PBGPU_OK)
+        return rc;
+    uint64_t body = 0, src_end = 0;
+    const int brc = pcap_body(ctx, src, first_frame, n, 0, &body, &src_end);
+    if (brc != PBGPU_OK)
+        return brc;
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    hipStream_t st = ctx->stream;
+    // a fixed-length source none of whose frames can split: no count, a plain copy
+    const bool copy = src->fixed_len && src->fixed_len <= opts->mtu + 14u;
+    pb_fgargs A;
+    frag_args(&A, src, first_frame, n, opts);
+    unsigned long long r[PB_FG_RES_DW] = {n, 0, 0, 0, src->fixed_len, src->fixed_len, 0, 0};
+    timing_pair tp = {nullptr, nullptr};
+    if (n)
+    {
+        const int prc = timed_pair(ctx, &tp);
+        if (prc != PBGPU_OK)
+            return prc;
+        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
+        HIPCHK(hipEventRecord(tp.a, st));
+        if (!copy)
+        {
+            // the count and scan run, and their result is read, before anything of dst is touched
+            const int crc = frag_count(ctx, &A, r);
+            if (crc != PBGPU_OK)
+                return crc;
+            HIPCHK(hipStreamSynchronize(st));
+            if (r[0] < n)
+                return PBGPU_EIO;
+        }
+    }
+    const uint64_t n_out = n ? r[0] : 0;
+    const uint64_t total = body + 34u * (n_out - n);
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    if (n && !copy && n_out > ctx->fg_map_cap)
+    {
+        if (ctx->d_fg_map)
+            (void)hipFree(ctx->d_fg_map);
+        ctx->d_fg_map = nullptr;
+        ctx->fg_map_cap = 0;
+        if (hipMalloc((void **)&ctx->d_fg_map, n_out * sizeof(uint64_t)) != hipSuccess)
+            return PBGPU_ENOMEM;
+        ctx->fg_map_cap = n_out;
+    }
+    frames_events *fe = frames_ev(dst);
+    if (fe == NULL)
+        return PBGPU_ENOMEM;
+    // as an upload: after dst's last build on another stream and the landings queued from it
+    if (fe->last && fe->last != st)
+    {
+        if (fe->moved == nullptr)
+            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fe->moved, fe->last));
+        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
+    }
+    fe->last = st;
+    fe->packed32 = false;
+    fe->up_max_len1 = (n && !copy) ? (uint32_t)r[5] + 1u : 0;
+    fe->min_len = n ? (uint32_t)r[4] : 0;
+    fe->max_len = n ? (uint32_t)r[5] : 0;
+    if (fe->land_pending)
+    {
+        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
+        fe->land_pending = false;
+    }
+    float ms = 0;
+    if (n)
+    {
+        A.dst = dst->data;
+        A.dst_offsets = dst->offsets;
+        A.map = ctx->d_fg_map;
+        A.n_out = n_out;
+        A.total = total;
+        A.end16 = end16;
+        // pages per workgroup as pbgpu_encap
+        const uint64_t npages = (end16 + 4095) >> 12;
+        uint64_t per = npages / 16384;
+        per = per < 1 ? 1 : (per > 32 ? 32 : per);
+        if ((npages + per - 1) / per > (1ull << 24))
+            per = (npages + (1ull << 24) - 1) >> 24;
+        if (per > 0xFFFFFFFFull)
+            return PBGPU_EINVAL;
+        A.per = (uint32_t)per;
+        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        HIPCHK(pbk_launch_frag(&A, copy ? 2 : 1, grid, st));
+        HIPCHK(hipEventRecord(tp.b, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = n_out;
+    dst->fixed_len = (n && copy) ? src->fixed_len : 0;
+    dst->total_bytes = total;
+    if (res)
+    {
+        memset(res, 0, sizeof *res);
+        res->n_in = n;
+        res->n_out = n_out;
+        res->n_split = n ? r[1] : 0;
+        res->n_df = n ? r[2] : 0;
+        res->n_other = n ? r[3] : 0;
+        res->out_bytes = total;
+        res->out_min_len = fe->min_len;
+        res->out_max_len = fe->max_len;
+        res->device_ms = ms;
+    }
+    return mark_built(ctx, dst, st);
+}
+
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
 {
     if (ctx == NULL || ptr == NULL)
@@ -3389,6 +3637,8 @@ size_t pbgpu_abi_size(int which)
     case 7: return sizeof(pbgpu_verify_result);
     case 8: return sizeof(pbgpu_pcap_opts);
     case 9: return sizeof(pbgpu_encap_opts);
+    case 10: return sizeof(pbgpu_frag_opts);
+    case 11: return sizeof(pbgpu_frag_result);
     default: return 0;
     }
 }

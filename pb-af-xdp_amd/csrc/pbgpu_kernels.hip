@@ -4867,3 +4867,427 @@ extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStr
         hipLaunchKernelGGL((pb_encap_kernel<false>), dim3(grid), dim3(PB_EN_WT), 0, st, *A);
     return hipGetLastError();
 }
+
+// ---------------- IPv4 fragmentation (pbgpu_fragment) ----------------
+// The output is the source byte stream with a 34-B header inserted before every fragment i >= 1
+// and three fields patched in every fragment's header; everything else sits at its source position
+// plus 34 times the number of insertions before it.  The output frame count depends on the data,
+// so three stages: count (K per source frame, their sums per workgroup, the result counts), scan
+// (pb_scan_blocks over the workgroup sums; pb_frag_map_kernel then writes dst->offsets and one map
+// entry per output record) and the destination-owned writer.
+
+__global__ __launch_bounds__(64) void pb_frag_init_kernel(unsigned long long *res)
+{
+    if (threadIdx.x < PB_FG_RES_DW)
+        res[threadIdx.x] = threadIdx.x == 4u ? 0xFFFFFFFFull : 0ull;
+}
+
+// Count: one lane per source frame, PB_FG_CB rows of 256 frames per workgroup (one K sum per row for
+// the scan; the result counts are kept in registers across the rows, so the atomics on the six
+// result words come once per 4,096 frames: at one per 256 they were most of this stage's time).
+// A frame that fits (L - 14 <= mtu) is never read; of the others bytes 12..23 come from aligned
+// dwords inside the frame (it is longer than 82 B).
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_count_kernel(pb_fgargs A)
+{
+    __shared__ uint32_t s_k[2][PB_FG_WT / 64u];
+    __shared__ uint32_t s_red[5 * (PB_FG_WT / 64u)];
+    const uint32_t tid = threadIdx.x, wv = tid >> 6;
+    const uint64_t nrow = (A.n + PB_FG_WT - 1u) / PB_FG_WT;
+    uint32_t split = 0, df = 0, other = 0, omin = 0xFFFFFFFFu, omax = 0;
+    for (uint32_t ri = 0; ri < PB_FG_CB; ++ri)
+    {
+        const uint64_t row = (uint64_t)blockIdx.x * PB_FG_CB + ri;
+        if (row >= nrow)
+            break;
+        const uint64_t j = row * PB_FG_WT + tid;
+        uint32_t K = 0;
+        if (j < A.n)
+        {
+            uint64_t o;
+            uint32_t L;
+            if (A.offsets)
+            {
+                o = A.offsets[A.first + j];
+                L = (uint32_t)(A.offsets[A.first + j + 1] - o);
+            }
+            else
+            {
+                o = (A.first + j) * A.fixed_len;
+                L = A.fixed_len;
+            }
+            K = 1;
+            uint32_t lmin = L, lmax = L;
+            if (L > A.mtu + 14u)
+            {
+                const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+                const uint64_t a = o + 12u, i = a >> 2;
+                const uint32_t sh = (uint32_t)a & 3u;
+                const uint32_t d0 = w[i], d1 = w[i + 1], d2 = w[i + 2], d3 = w[i + 3];
+                const uint32_t b12 = __builtin_amdgcn_alignbyte(d1, d0, sh); // bytes 12..15
+                const uint32_t b20 = __builtin_amdgcn_alignbyte(d3, d2, sh); // bytes 20..23
+                const uint32_t fo = pb_bswap16(b20 & 0xFFFFu);
+                if ((b12 & 0x00FFFFFFu) != 0x00450008u)
+                    other += 1;
+                else if ((fo & 0x4000u) && !(A.flags & PB_FG_IGNORE_DF))
+                    df += 1;
+                else
+                {
+                    const uint32_t D = L - 34u;
+                    K = pb_divq(D + A.C - 1u, A.cdiv);
+                    split += 1;
+                    lmax = 34u + A.C;
+                    lmin = 34u + D - (K - 1u) * A.C;
+                }
+            }
+            omin = lmin < omin ? lmin : omin;
+            omax = lmax > omax ? lmax : omax;
+            A.kcnt[j] = K;
+        }
+        uint32_t sumK = K;
+#pragma unroll
+        for (uint32_t dd = 32; dd > 0; dd >>= 1)
+            sumK += __shfl_xor(sumK, dd, 64);
+        if ((tid & 63u) == 0)
+            s_k[ri & 1u][wv] = sumK; // two sets: a row's readers and the next row's writers never meet
+        __syncthreads();
+        if (tid == 0)
+        {
+            uint32_t t = 0;
+#pragma unroll
+            for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
+                t += s_k[ri & 1u][v];
+            A.bsum[row] = t;
+        }
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+    {
+        split += __shfl_xor(split, dd, 64);
+        df += __shfl_xor(df, dd, 64);
+        other += __shfl_xor(other, dd, 64);
+        const uint32_t mn = __shfl_xor(omin, dd, 64), mx = __shfl_xor(omax, dd, 64);
+        omin = mn < omin ? mn : omin;
+        omax = mx > omax ? mx : omax;
+    }
+    if ((tid & 63u) == 0)
+    {
+        s_red[5 * wv + 0] = split, s_red[5 * wv + 1] = df, s_red[5 * wv + 2] = other;
+        s_red[5 * wv + 3] = omin, s_red[5 * wv + 4] = omax;
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        uint32_t r[5] = {0, 0, 0, 0xFFFFFFFFu, 0};
+#pragma unroll
+        for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
+        {
+            r[0] += s_red[5 * v + 0], r[1] += s_red[5 * v + 1], r[2] += s_red[5 * v + 2];
+            r[3] = s_red[5 * v + 3] < r[3] ? s_red[5 * v + 3] : r[3];
+            r[4] = s_red[5 * v + 4] > r[4] ? s_red[5 * v + 4] : r[4];
+        }
+        if (r[0])
+            atomicAdd(A.res + 1, (unsigned long long)r[0]);
+        if (r[1])
+            atomicAdd(A.res + 2, (unsigned long long)r[1]);
+        if (r[2])
+            atomicAdd(A.res + 3, (unsigned long long)r[2]);
+        atomicMin(A.res + 4, (unsigned long long)r[3]);
+        atomicMax(A.res + 5, (unsigned long long)r[4]);
+    }
+}
+
+// Offsets and map: one lane per source frame.  F(j), the output records before frame j, from the
+// scanned workgroup sums and a workgroup scan of K; the frame's first record starts at
+// off(j) - off(first) + 34 (F(j) - j) and every further one 34 + C after the last.
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_map_kernel(pb_fgargs A)
+{
+    __shared__ uint32_t s_w[PB_FG_WT / 64u];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t j = (uint64_t)blockIdx.x * PB_FG_WT + tid;
+    const uint32_t K = j < A.n ? A.kcnt[j] : 0u;
+    const uint32_t inc = pb_wave_scan(K);
+    if ((tid & 63u) == 63u)
+        s_w[tid >> 6] = inc;
+    __syncthreads();
+    uint32_t pre = inc - K;
+    for (uint32_t v = 0; v < (tid >> 6); ++v)
+        pre += s_w[v];
+    if (j >= A.n)
+        return;
+    const uint64_t F = A.bsum[blockIdx.x] + pre;
+    uint64_t o, ob;
+    uint32_t L;
+    if (A.offsets)
+    {
+        ob = A.offsets[A.first];
+        o = A.offsets[A.first + j];
+        L = (uint32_t)(A.offsets[A.first + j + 1] - o);
+    }
+    else
+    {
+        ob = A.first * A.fixed_len;
+        o = (A.first + j) * A.fixed_len;
+        L = A.fixed_len;
+    }
+    const uint64_t O = (o - ob) + 34u * (F - j);
+    if (K == 1u)
+    {
+        A.dst_offsets[F] = O;
+        A.map[F] = o;
+    }
+    else
+    {
+        const uint32_t step = 34u + A.C;
+        for (uint32_t i = 0; i < K; ++i)
+        {
+            A.dst_offsets[F + i] = O + (uint64_t)i * step;
+            A.map[F + i] = o | ((uint64_t)(i | PB_FG_M_SPLIT | (i + 1u == K ? PB_FG_M_LAST : 0u)) << PB_FG_M_ISH);
+        }
+    }
+    if (j + 1u == A.n)
+        A.dst_offsets[F + K] = O + L + 34u * (K - 1u);
+}
+
+// the last k in [lo, hi] with s_rel[k] <= d (s_rel[lo] <= d)
+__device__ __forceinline__ uint32_t pb_fg_find(const uint32_t *s_rel, uint32_t d, uint32_t lo, uint32_t hi)
+{
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (s_rel[mid] <= d)
+            lo = mid;
+        else
+            hi = mid - 1u;
+    }
+    return lo;
+}
+
+// Writer, destination-owned as pb_encap_kernel: a workgroup owns `per` consecutive 4-KiB pages of
+// the output, a lane one aligned 16-B chunk of a page per step.  A window of record positions, source
+// positions and map bits is kept in LDS from page to page.  Per page one lane per fragment touching
+// it stages that fragment's 34-B header: the source frame's, with tot_len, the fragment field and
+// the checksum replaced, moved to the alignment it has in the output.  Every byte of a chunk that is
+// not in a staged header comes from the source at one shift: the one of the data of the record
+// holding the chunk's first byte (between two insertions the shift is constant, an inserted header
+// is longer than a chunk, and a record shorter than a chunk is never a fragment).  At most three
+// records' headers can reach into a chunk; a wave none of whose chunks meets a staged header or the
+// output's end takes the plain shifted copy, chosen per wave.
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
+{
+    __shared__ uint32_t s_rel[PB_FG_WIN];  // output start of record f0 + k relative to record f0's; 0xFFFFFFFF past the end
+    __shared__ uint32_t s_h[PB_FG_WIN];    // its source frame's offset in src relative to record f0's
+    __shared__ uint32_t s_meta[PB_FG_WIN]; // map entry >> 48; 0 past the last record
+    __shared__ uint32_t s_hdr[PB_FG_HREC * PB_FG_HDW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+    const uint64_t hmask = (1ull << PB_FG_M_ISH) - 1u;
+    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
+    if (p >= A.end16)
+        return;
+    // f0: the record holding the first page's first byte (p is below the output's last byte)
+    uint64_t f0 = 0;
+    {
+        uint64_t lo = 0, hi = A.n_out - 1u;
+        while (lo < hi)
+        {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (A.dst_offsets[mid] <= p)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        f0 = lo;
+    }
+    int32_t d0 = (int32_t)(p - A.dst_offsets[f0]); // the page's first byte relative to record f0's start
+    uint64_t hbase = 0;
+    bool have_win = false;
+    uint32_t kw = 0; // the window's index of the record holding the page's first byte
+    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    {
+        if (!have_win || (int64_t)s_rel[PB_FG_WIN - 1u] <= (int64_t)d0 + 4095)
+        {
+            if (have_win) // the window moves to that record
+            {
+                f0 += kw;
+                d0 -= (int32_t)s_rel[kw];
+            }
+            __syncthreads(); // the window's readers are done
+            const uint64_t g = A.dst_offsets[f0];
+            hbase = A.map[f0] & hmask;
+            for (uint32_t k = tid; k < PB_FG_WIN; k += PB_FG_WT)
+            {
+                const uint64_t ff = f0 + k;
+                uint32_t rel = 0xFFFFFFFFu, hh = 0, mm = 0;
+                if (ff <= A.n_out)
+                    rel = (uint32_t)(A.dst_offsets[ff] - g);
+                if (ff < A.n_out)
+                {
+                    const uint64_t m = A.map[ff];
+                    hh = (uint32_t)((m & hmask) - hbase);
+                    mm = (uint32_t)(m >> PB_FG_M_ISH);
+                }
+                s_rel[k] = rel, s_h[k] = hh, s_meta[k] = mm;
+            }
+            have_win = true;
+            kw = 0;
+        }
+        __syncthreads(); // the window is in place, the last page's header readers are done
+        // the record holding the page's last byte: the one search of the window per page; a chunk
+        // then searches the page's records only (two steps at 1514-B records)
+        const uint32_t khi = kw + PB_FG_HREC - 1u < PB_FG_WIN - 1u ? kw + PB_FG_HREC - 1u : PB_FG_WIN - 1u;
+        const uint32_t kend = pb_fg_find(s_rel, (uint32_t)d0 + 4095u, kw, khi);
+
+        // ---- header stage: the i-th record touching the page, if it is a fragment ----
+        for (uint32_t i = tid; kw + i <= kend; i += PB_FG_WT)
+        {
+            const uint32_t k = kw + i;
+            if (k + 1u >= PB_FG_WIN)
+                continue;
+            const uint32_t rs = s_rel[k], re = s_rel[k + 1u], meta = s_meta[k];
+            if (!(meta & PB_FG_M_SPLIT) || (int64_t)rs >= (int64_t)d0 + 4096)
+                continue;
+            // the source frame's first 34 bytes (the frame is longer than 82 B)
+            const uint64_t hsrc = hbase + s_h[k], i0 = hsrc >> 2;
+            const uint32_t sh = (uint32_t)hsrc & 3u;
+            uint32_t dd[10], T[PB_FG_HDW];
+#pragma unroll
+            for (uint32_t u = 0; u < 10u; ++u)
+                dd[u] = w[i0 + u];
+#pragma unroll
+            for (uint32_t u = 0; u < 9u; ++u)
+                T[u] = __builtin_amdgcn_alignbyte(dd[u + 1u], dd[u], sh);
+            T[9] = 0u;
+            const uint32_t fo = pb_bswap16(T[5] & 0xFFFFu);
+            const uint32_t tot = re - rs - 14u;
+            const uint32_t mf = (meta & PB_FG_M_LAST) ? (fo & 0x2000u) : 0x2000u;
+            const uint32_t frag = (fo & 0xC000u) | mf | (((fo & 0x1FFFu) + (meta & 0x7FFu) * (A.C >> 3)) & 0x1FFFu);
+            // the unchanged header words + tot_len + the fragment field, as little-endian halves: the
+            // one's complement sum commutes with the byte swap
+            const uint32_t s = (T[3] >> 16) + (T[4] >> 16) + (T[5] >> 16) + (T[6] >> 16) + pb_halves(T[7]) +
+                               (T[8] & 0xFFFFu) + pb_bswap16(tot) + pb_bswap16(frag);
+            T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
+            T[5] = (T[5] & 0xFFFF0000u) | pb_bswap16(frag);
+            T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
+            // moved to the output's alignment: staged dword u is output bytes hb + 4u .. + 3, hb the
+            // header's first byte rounded down to 4
+            const int32_t hs = (int32_t)rs - d0; // the header's first byte in the page (below 0: before it)
+            const uint32_t sh2 = (uint32_t)hs & 3u;
+            uint32_t *slot = s_hdr + i * PB_FG_HDW;
+#pragma unroll
+            for (uint32_t u = 0; u < PB_FG_HDW; ++u)
+                slot[u] = sh2 ? __builtin_amdgcn_alignbyte(T[u], u ? T[u - 1u] : 0u, 4u - sh2) : T[u];
+        }
+        __syncthreads();
+
+        // ---- chunks ----
+        const int32_t d = d0 + 16 * (int32_t)tid;
+        const uint64_t pc = p + 16u * tid;
+        if (pc < A.end16)
+        {
+            // the chunk starts r bytes into record f0 + k (pc is below the output's last byte)
+            const uint32_t k = pb_fg_find(s_rel, (uint32_t)d, kw, kend);
+            const uint32_t rs = s_rel[k], meta = s_meta[k];
+            const int32_t r = d - (int32_t)rs;
+            const bool frag = (meta & PB_FG_M_SPLIT) != 0u;
+            // the chunk's first byte in src, as data of its record
+            const int64_t a = (int64_t)(hbase + s_h[k]) + (frag ? (meta & 0x7FFu) * A.C : 0u) + r;
+            const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
+            bool slow = (frag && r < 34) || hi < 16;
+#pragma unroll
+            for (uint32_t c = 1; c < 3u; ++c)
+                slow = slow || (k + c < PB_FG_WIN && (s_meta[k + c] & PB_FG_M_SPLIT) && s_rel[k + c] < (uint32_t)(d + 16));
+            pb_u32x4 v;
+            if (__ballot(slow) == 0ull)
+            {
+                const uint64_t i = (uint64_t)a >> 2;
+                const uint32_t sh = (uint32_t)a & 3u;
+                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
+                const uint32_t w4 = sh ? w[i + 4] : 0u; // off alignment it still holds a byte of the chunk
+                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
+                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
+                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+            }
+            else
+            {
+                uint32_t o4[4] = {0u, 0u, 0u, 0u};
+                const int32_t lo = (frag && r < 34) ? 34 - r : 0; // the record's data starts here
+                if (lo < hi)
+                    pb_en_gather(w, a, lo, hi, o4);
+#pragma unroll
+                for (uint32_t c = 0; c < 3u; ++c)
+                {
+                    const uint32_t kk = k + c;
+                    if (kk < PB_FG_WIN && (s_meta[kk] & PB_FG_M_SPLIT))
+                    {
+                        const int32_t sa = (int32_t)s_rel[kk] - d, sb = sa + 34; // the header, in the chunk's bytes
+                        if (sa < 16 && sb > 0)
+                        {
+                            const uint32_t *slot = s_hdr + (kk - kw) * PB_FG_HDW;
+                            const int32_t hsp = (int32_t)s_rel[kk] - d0;
+                            const int32_t ub = (16 * (int32_t)tid - (hsp & ~3)) >> 2;
+#pragma unroll
+                            for (int t = 0; t < 4; ++t)
+                            {
+                                const uint32_t val = (uint32_t)(ub + t) < PB_FG_HDW ? slot[(uint32_t)(ub + t)] : 0u;
+                                const uint32_t m = pb_en_lt(4 * t, sb) & ~pb_en_lt(4 * t, sa);
+                                o4[t] = (o4[t] & ~m) | (val & m);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    o4[t] &= pb_en_lt(4 * t, hi); // zeros past the output's last byte
+                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+            }
+            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
+        }
+        // the next page's first byte is in the record holding this page's last byte, or the one after
+        d0 += 4096;
+        kw = s_rel[kend + 1u] <= (uint32_t)d0 ? kend + 1u : kend;
+    }
+}
+
+// A fixed-length source none of whose frames can split: the range's bytes copied to byte 0 of dst,
+// zeros up to the next multiple of 16.  Pages and chunks as the writer's.
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_copy_kernel(pb_fgargs A)
+{
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+    const uint64_t a0 = A.first * A.fixed_len;
+    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12;
+    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    {
+        const uint64_t pc = p + 16u * threadIdx.x;
+        if (pc >= A.end16)
+            continue;
+        const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
+        uint32_t o4[4];
+        pb_en_gather(w, (int64_t)(a0 + pc), 0, hi, o4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            o4[t] &= pb_en_lt(4 * t, hi);
+        *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+    }
+}
+
+// stage 0: the result words, the count and the scan of its workgroup sums (the total lands in
+// res[0]); stage 1: dst->offsets, the map and the writer; stage 2: the plain copy
+extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st)
+{
+    const uint32_t nblk = (uint32_t)((A->n + PB_FG_WT - 1u) / PB_FG_WT);
+    if (stage == 0)
+    {
+        hipLaunchKernelGGL(pb_frag_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_frag_count_kernel, dim3((nblk + PB_FG_CB - 1u) / PB_FG_CB), dim3(PB_FG_WT), 0, st, *A);
+        hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->bsum, nblk, (uint64_t *)A->res, (uint64_t)0);
+    }
+    else if (stage == 1)
+    {
+        hipLaunchKernelGGL(pb_frag_map_kernel, dim3(nblk), dim3(PB_FG_WT), 0, st, *A);
+        hipLaunchKernelGGL(pb_frag_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, *A);
+    }
+    else
+        hipLaunchKernelGGL(pb_frag_copy_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, *A);
+    return hipGetLastError();
+}

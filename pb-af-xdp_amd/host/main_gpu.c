@@ -41,6 +41,9 @@ static uint64_t pcapt0_ns;
 /* --encap vlan:VID[:PCP] | vxlan:VNI:SRCIP:DSTIP[:DPORT], once: handed to the driver with pb_set_encap */
 static const char *encap_spec;
 static int encap_twice;
+/* --fragment MTU[:ignoredf], once: handed to the driver with pb_set_fragment */
+static const char *fragment_spec;
+static int fragment_twice;
 
 static void sign_hdl(int sig)
 {
@@ -53,7 +56,7 @@ enum
     O_INTERFACE = 256, O_BLOCK, O_TRACK, O_MAXPCKTS, O_MAXBYTES, O_PPS, O_BPS, O_DELAY, O_THREADS, O_L4CSUM, O_SMAC,
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
-    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP,
+    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT,
 };
 
 static const struct option common_opts[] = {
@@ -93,7 +96,7 @@ static const struct option common_opts[] = {
     {"umemframes", required_argument, NULL, O_SECOND_PASS}, {"umemslot", required_argument, NULL, O_SECOND_PASS},
     {"verify", no_argument, NULL, O_SECOND_PASS},
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
-    {"encap", required_argument, NULL, O_ENCAP},
+    {"encap", required_argument, NULL, O_ENCAP}, {"fragment", required_argument, NULL, O_FRAGMENT},
     {NULL, 0, NULL, 0},
 };
 
@@ -182,6 +185,11 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
             if (encap_spec && encap_spec != a)
                 encap_twice = 1;
             encap_spec = a;
+            break;
+        case O_FRAGMENT:
+            if (fragment_spec && fragment_spec != a)
+                fragment_twice = 1;
+            fragment_spec = a;
             break;
         default: break;
         }
@@ -286,6 +294,39 @@ static int parse_encap(const char *spec, pbgpu_encap_opts *o, const char **why)
     return -1;
 }
 
+/* --fragment's argument MTU[:ignoredf] -> the options; -1 and a message in `why` for a malformed one */
+static int parse_fragment(const char *spec, pbgpu_frag_opts *o, const char **why)
+{
+    char buf[32];
+    memset(o, 0, sizeof *o);
+    if (strlen(spec) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    strcpy(buf, spec);
+    char *opt = strchr(buf, ':');
+    if (opt)
+        *opt++ = '\0';
+    uint32_t v = 0;
+    if (field_u32(buf, 65535, &v) != 0 || v < 68)
+    {
+        *why = "MTU is 68-65535";
+        return -1;
+    }
+    o->mtu = v;
+    if (opt)
+    {
+        if (strcmp(opt, "ignoredf") != 0)
+        {
+            *why = "expected MTU[:ignoredf]";
+            return -1;
+        }
+        o->flags = PBGPU_FRAG_IGNORE_DF;
+    }
+    return 0;
+}
+
 static void print_cmd_help(void)
 {
     fprintf(stdout, "Usage: pcktbatch-gpu -c <configfile> | -z [overrides] [-v -l -h] [AF_XDP/GPU options]\n\n"
@@ -296,14 +337,17 @@ static void print_cmd_help(void)
                     "-z --cli => Enables the first sequence/packet override (README.md first-sequence options).\n\n"
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
-                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC\n"
+                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf]\n"
                     "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
                     "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
                     "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
                     "1/pps per frame.\n"
                     "--encap vlan:VID[:PCP] | vxlan:VNI:SRCIP:DSTIP[:DPORT] => Encapsulate every frame on the GPU before "
                     "it is sent or dumped: an 802.1Q tag, or a VXLAN outer header (the sequence's MACs, TTL 64, source "
-                    "port hashed from the inner frame, DPORT 4789 by default).\n");
+                    "port hashed from the inner frame, DPORT 4789 by default).\n"
+                    "--fragment MTU[:ignoredf] => Split every built IPv4 packet longer than MTU (68-65535) into fragments "
+                    "on the GPU before it is verified again, encapsulated, sent or dumped; packets with DF set are left "
+                    "whole unless :ignoredf is given. --maxpckts counts built packets, the byte limits what is sent.\n");
 }
 
 int main(int argc, char **argv)
@@ -349,6 +393,22 @@ int main(int argc, char **argv)
             return EXIT_FAILURE;
         }
         pb_set_encap(&eo);
+    }
+    if (fragment_spec)
+    {
+        pbgpu_frag_opts fo;
+        const char *why = NULL;
+        if (fragment_twice)
+        {
+            fprintf(stderr, "--fragment given more than once: one MTU per run.\n");
+            return EXIT_FAILURE;
+        }
+        if (parse_fragment(fragment_spec, &fo, &why) != 0)
+        {
+            fprintf(stderr, "--fragment %s: %s.\n", fragment_spec, why);
+            return EXIT_FAILURE;
+        }
+        pb_set_fragment(&fo);
     }
     struct cmd_line_af_xdp cmd_af_xdp = {0};
     cmd_line_af_xdp_defaults(&cmd_af_xdp);

@@ -2,7 +2,8 @@
  * pcap_dump.c — pcktbatch-gpu --pcapdump (pcap_dump.h).
  *
  * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
- * Batch k is (verified, with --encap encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
+ * Batch k is (verified, with --fragment fragmented into a fragment buffer and verified again, with --encap
+ * encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
  * other frame buffer; then stream k is copied to its host buffer in one piece and written with
  * one write() per buffer (looped only on a short write).
  */
@@ -81,16 +82,18 @@ typedef struct dump_state
 
 /* One sequence: frames [0, max_pckts) stamped from t0_ns; *n_done = the frames written. */
 static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx, uint64_t t0_ns, uint64_t step_ps,
-                         uint64_t *n_done, uint64_t *n_verified, uint64_t *n_bad)
+                         uint64_t *n_done, uint64_t *n_verified, uint64_t *n_bad, uint64_t *n_packed, uint64_t *b_packed)
 {
     const int seq_num = idx + 1;
     pbgpu_ctx *ctx = D->ctx;
     pbgpu_frames *src[2] = {NULL, NULL}, *dst[2] = {NULL, NULL};
     pbgpu_frames *enc = NULL; /* --encap: the batch as it is packed (the pack returns before the next encap) */
+    pbgpu_frames *frg = NULL; /* --fragment: the batch's fragments (what is encapsulated, or packed) */
     uint8_t *hb[2] = {NULL, NULL};
     int reg[2] = {0, 0};
     int rc;
-    uint64_t done = 0, iter = 0; /* frames written; the current batch's first iteration */
+    uint64_t done = 0, iter = 0; /* built frames written; the current batch's first iteration */
+    uint64_t packed = 0, packed_b = 0; /* frames packed (--fragment: fragments) and their bytes */
     pb_rules_t rules;
     uint8_t smac[6], dmac[6];
     pb_seq_prepare(seq, D->device, D->cmd, seq_num, &rules, smac, dmac);
@@ -122,8 +125,24 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
             break;
         batch >>= 1;
     }
-    const uint64_t cap = 24 + (16 + extra) * mf + mb + 16;
-    if (encap && (rc = pbgpu_frames_alloc(ctx, mf, mb + extra * mf + 16, &enc)) != 0)
+    /* --fragment: pbgpu_fragment_bound's arithmetic for the sequence's longest frame (16 iterations:
+     * the size bound is then the frames times that frame, plus 16) */
+    const pbgpu_frag_opts *fo = pb_get_fragment();
+    uint64_t of = mf, obytes = mb; /* the frames and bytes a batch can become before it is encapsulated */
+    if (fo)
+    {
+        uint64_t f16 = 0, b16 = 0;
+        if ((rc = pbgpu_build_size(ctx, idx, 16, &f16, &b16)) != 0)
+            goto out;
+        const uint64_t longest = f16 ? (b16 - 16) / f16 : 0, c = (fo->mtu - 20u) & ~7u;
+        const uint64_t kmax = longest > fo->mtu + 14ull ? (longest - 34 + c - 1) / c : 1;
+        of = mf * kmax;
+        obytes = mb + 34 * mf * (kmax - 1) + 16;
+        if ((rc = pbgpu_frames_alloc(ctx, of, obytes, &frg)) != 0)
+            goto out;
+    }
+    const uint64_t cap = 24 + (16 + extra) * of + obytes + 16;
+    if (encap && (rc = pbgpu_frames_alloc(ctx, of, obytes + extra * of + 16, &enc)) != 0)
         goto out;
     const size_t page = (size_t)sysconf(_SC_PAGESIZE);
     for (int i = 0; i < 2; ++i)
@@ -170,7 +189,37 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         }
         const uint64_t have = src[cur]->n_frames;
         const uint64_t take = have < quota - done ? have : quota - done; /* the last batch: up to the quota */
-        if (encap && (rc = pbgpu_encap(ctx, src[cur], 0, take, &eopts, enc, NULL)) != 0)
+        pbgpu_frames *bf = src[cur]; /* the batch as it is encapsulated or packed, and its frames */
+        uint64_t btake = take;
+        if (fo)
+        {
+            if ((rc = pbgpu_fragment(ctx, src[cur], 0, take, fo, frg, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error fragmenting frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc));
+                goto out;
+            }
+            bf = frg;
+            btake = frg->n_frames;
+            if (D->cmd->verify) /* a fragment has no L4 checksum of its own */
+            {
+                pbgpu_verify_result r;
+                if ((rc = pbgpu_verify(ctx, frg, 0, btake, PBGPU_VERIFY_IP_CSUM | PBGPU_VERIFY_TOT_LEN, &r, NULL)) != 0)
+                {
+                    fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                            pbgpu_strerror(rc));
+                    goto out;
+                }
+                if (r.n_bad)
+                {
+                    *n_bad += r.n_bad;
+                    pb_verify_failed_msg(seq_num, r.n_bad, r.first_bad, iter);
+                    rc = PBGPU_EIO;
+                    goto out;
+                }
+            }
+        }
+        if (encap && (rc = pbgpu_encap(ctx, bf, 0, btake, &eopts, enc, NULL)) != 0)
         {
             fprintf(stderr, "[%d] Error encapsulating frames on GPU %d :: %s%s.\n", seq_num, D->cmd->gpu_first,
                     pbgpu_strerror(rc), rc == PBGPU_EINVAL ? " (a frame too long for the outer header?)" : "");
@@ -180,15 +229,17 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         memset(&o, 0, sizeof o);
         o.t0_ns = t0_ns;
         o.step_ps = step_ps;
-        o.first_index = done;
+        o.first_index = packed; /* timestamps index the frames packed */
         o.flags = D->header_due ? PBGPU_PCAP_FILE_HEADER : 0u;
         uint64_t nbytes = 0;
-        if ((rc = pbgpu_pcap_pack(ctx, encap ? enc : src[cur], 0, take, &o, dst[cur], &nbytes, NULL)) != 0)
+        if ((rc = pbgpu_pcap_pack(ctx, encap ? enc : bf, 0, btake, &o, dst[cur], &nbytes, NULL)) != 0)
         {
             fprintf(stderr, "[%d] Error packing the pcap stream on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
                     pbgpu_strerror(rc));
             goto out;
         }
+        packed += btake;
+        packed_b += nbytes - (D->header_due ? 24u : 0u) - 16u * btake;
         D->header_due = 0;
         /* the next batch builds while this one's stream crosses the host link and is written */
         const uint64_t left = quota - done - take;
@@ -232,7 +283,10 @@ out:
         pbgpu_frames_free(ctx, src[i]);
     }
     pbgpu_frames_free(ctx, enc);
+    pbgpu_frames_free(ctx, frg);
     *n_done = done;
+    *n_packed = packed;
+    *b_packed = packed_b;
     return rc;
 }
 
@@ -269,6 +323,7 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         return PBGPU_EIO;
     }
     uint64_t verified[PB_MAX_SEQUENCES] = {0}, bad[PB_MAX_SEQUENCES] = {0}, written[PB_MAX_SEQUENCES] = {0};
+    uint64_t packed[PB_MAX_SEQUENCES] = {0}, packed_b[PB_MAX_SEQUENCES] = {0};
     time_t secs[PB_MAX_SEQUENCES] = {0};
     int ran = 0;
     for (int i = 0; i < seq_cnt && rc == 0 && !pb_stop_requested(); ++i)
@@ -283,10 +338,10 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         const uint64_t step_ps = seq->pps > 0 ? 1000000000000ull / seq->pps : 0;
         uint64_t n = 0;
         const time_t t_start = time(NULL);
-        rc = dump_sequence(&D, seq, (uint16_t)i, t0_ns, step_ps, &n, &verified[i], &bad[i]);
+        rc = dump_sequence(&D, seq, (uint16_t)i, t0_ns, step_ps, &n, &verified[i], &bad[i], &packed[i], &packed_b[i]);
         secs[i] = time(NULL) - t_start;
         /* the next sequence continues where this one's clock stopped */
-        t0_ns += (uint64_t)((unsigned __int128)n * step_ps / 1000u);
+        t0_ns += (uint64_t)((unsigned __int128)packed[i] * step_ps / 1000u);
         written[i] = n;
     }
     if (D.header_due && rc == 0) /* nothing was packed: still a well-formed (empty) capture */
@@ -305,11 +360,17 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         rc = crc;
     fprintf(stdout, "Completed %d sequences!\n", ran);
     /* --encap: the library counts the frames as built; the file holds the header bytes as well */
-    if (pb_get_encap())
+    if (pb_get_encap() && !pb_get_fragment())
         for (int i = 0; i < ran; ++i)
             b[i] += written[i] * (pb_get_encap()->mode == PBGPU_ENCAP_VLAN ? 4u : 50u);
     for (int i = 0; i < ran; ++i)
-        pb_print_sequence_total(i + 1, p[i], b[i], secs[i]);
+    {
+        /* --fragment: the packets are the built ones (the quota's), the bytes what the file holds, and
+         * the frames packed follow on a line of their own */
+        pb_print_sequence_total(i + 1, p[i], pb_get_fragment() ? packed_b[i] : b[i], secs[i]);
+        if (pb_get_fragment())
+            fprintf(stdout, "[%d] Fragmented into %llu frames.\n", i + 1, (unsigned long long)packed[i]);
+    }
     for (int i = 0; i < ran && cmd->verify; ++i)
         pb_print_verified(verified[i], bad[i]);
     fflush(stdout);

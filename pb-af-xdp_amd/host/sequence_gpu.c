@@ -60,6 +60,8 @@ static void *tx_ctx;
 static volatile int stop_requested;
 static int encap_on; /* --encap (pb_set_encap) */
 static pbgpu_encap_opts encap_opts;
+static int frag_on; /* --fragment (pb_set_fragment) */
+static pbgpu_frag_opts frag_opts;
 
 void pb_request_stop(void)
 {
@@ -92,6 +94,18 @@ void pb_set_encap(const pbgpu_encap_opts *opts)
 const pbgpu_encap_opts *pb_get_encap(void)
 {
     return encap_on ? &encap_opts : NULL;
+}
+
+void pb_set_fragment(const pbgpu_frag_opts *opts)
+{
+    frag_on = opts != NULL;
+    if (opts)
+        frag_opts = *opts;
+}
+
+const pbgpu_frag_opts *pb_get_fragment(void)
+{
+    return frag_on ? &frag_opts : NULL;
 }
 
 int pb_last_error(void)
@@ -207,6 +221,28 @@ static int gb_encap(void *h, void *src, const pbgpu_encap_opts *opts, void *dst)
     pbgpu_frames *f = (pbgpu_frames *)src;
     return pbgpu_encap((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
 }
+static int gb_alloc_frag(void *h, uint16_t i, uint64_t n_iter, const pbgpu_frag_opts *opts, uint32_t extra,
+                         void **frames, uint32_t *max_len)
+{
+    /* the sequence's longest frame as in gb_alloc_encap; then pbgpu_fragment_bound's arithmetic */
+    uint64_t mf = 0, mb = 0;
+    int rc = pbgpu_build_size((pbgpu_ctx *)h, i, 16, &mf, &mb);
+    if (rc != 0 || mf == 0)
+        return rc ? rc : PBGPU_EINVAL;
+    const uint64_t longest = (mb - 16) / mf, c = (opts->mtu - 20u) & ~7u;
+    const uint64_t kmax = longest > opts->mtu + 14ull ? (longest - 34 + c - 1) / c : 1;
+    /* a built frame is IPv4 without options and without DF: one longer than the MTU allows is split */
+    *max_len = (uint32_t)(longest > opts->mtu + 14ull ? opts->mtu + 14ull : longest);
+    if ((rc = pbgpu_build_size((pbgpu_ctx *)h, i, n_iter, &mf, &mb)) == 0)
+        rc = pbgpu_frames_alloc((pbgpu_ctx *)h, mf * kmax, mb + mf * (kmax - 1) * 34 + mf * kmax * extra + 16,
+                                (pbgpu_frames **)frames);
+    return rc;
+}
+static int gb_fragment(void *h, void *src, const pbgpu_frag_opts *opts, void *dst)
+{
+    pbgpu_frames *f = (pbgpu_frames *)src;
+    return pbgpu_fragment((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -218,7 +254,7 @@ static void gb_close(void *h)
 
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
-                                         gb_verify, gb_alloc_encap, gb_encap};
+                                         gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -367,7 +403,8 @@ static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, c
             src = sip;
         }
         const uint32_t l4 = 14u + 4u * (fr[14] & 0xFu);
-        if ((fr[23] == 17 || fr[23] == 6) && l4 + 4u <= len)
+        /* a fragment past the first (--fragment) carries no L4 header: ports 0 */
+        if ((fr[23] == 17 || fr[23] == 6) && l4 + 4u <= len && (fr[20] & 0x1Fu) == 0 && fr[21] == 0)
         {
             sport = ((uint32_t)fr[l4] << 8) | fr[l4 + 1];
             dport = ((uint32_t)fr[l4 + 2] << 8) | fr[l4 + 3];
@@ -449,6 +486,7 @@ static void *gpu_worker(void *p)
     void *ctx = NULL;
     void *fr[2] = {NULL, NULL};
     void *efr[2] = {NULL, NULL}; /* --encap: what is landed */
+    void *ffr[2] = {NULL, NULL}; /* --fragment: the batch's fragments (what is encapsulated, or landed) */
     uint8_t *umem = NULL;
     int registered = 0;
     pb_xsk_t xsk;
@@ -497,9 +535,19 @@ static void *gpu_worker(void *p)
     const uint32_t enc_extra = enc ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u;
     memcpy(eopts.dst_mac, dmac, 6);
     memcpy(eopts.src_mac, smac, 6);
+    /* --fragment: a frame's fragments carry 34 more bytes each but the first (and the encapsulation's
+     * bytes each), so a batch of them still fits the byte bound */
+    const int frg = frag_on;
+    const pbgpu_frag_opts fopts = frag_opts;
+    uint64_t batch_flen = max_flen + enc_extra; /* bytes a built frame can become */
+    if (frg && max_flen > fopts.mtu + 14u)
+    {
+        const uint32_t c = (fopts.mtu - 20u) & ~7u, kmax = (max_flen - 34u + c - 1u) / c;
+        batch_flen = max_flen + (uint64_t)(kmax - 1u) * 34u + (uint64_t)kmax * enc_extra;
+    }
     max_flen += enc_extra;
     uint64_t batch = w->cmd.gpu_batch ? w->cmd.gpu_batch : (1u << 20);
-    while (batch > 1 && batch * fpi * max_flen > PB_BATCH_BYTES_MAX)
+    while (batch > 1 && batch * fpi * batch_flen > PB_BATCH_BYTES_MAX)
         batch >>= 1;
     /* launch-level pacing: one launch covers at most ~1/10 s of the configured rate
      * (pps and bps are global over the sequence's threads; delay is per thread
@@ -538,11 +586,24 @@ static void *gpu_worker(void *p)
         last_error = rc;
         goto out;
     }
+    if (frg)
+    {
+        uint32_t longest = 0;
+        if ((rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, 0, &ffr[0], &longest)) != 0 ||
+            (rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, 0, &ffr[1], &longest)) != 0)
+        {
+            last_error = rc;
+            goto out;
+        }
+    }
     if (enc)
     {
         uint32_t longest = 0;
-        if ((rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[0], &longest)) != 0 ||
-            (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[1], &longest)) != 0)
+        /* from the fragment buffer: sized for the fragments, and the longest frame is a fragment's */
+        if (frg ? (rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, enc_extra, &efr[0], &longest)) != 0 ||
+                      (rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, enc_extra, &efr[1], &longest)) != 0
+                : (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[0], &longest)) != 0 ||
+                      (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[1], &longest)) != 0)
         {
             last_error = rc;
             goto out;
@@ -684,9 +745,40 @@ static void *gpu_worker(void *p)
                 break;
             }
         }
+        if (frg)
+        {
+            if ((rc = B->fragment(ctx, fr[cur], &fopts, ffr[cur])) != 0)
+            {
+                fprintf(stderr, "[%d] Error fragmenting frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+            /* a fragment has no L4 checksum of its own: its IPv4 checksum and length are checked */
+            if (w->cmd.verify)
+            {
+                uint64_t bad = 0, first_bad = 0;
+                if ((rc = B->verify(ctx, ffr[cur], PBGPU_VERIFY_IP_CSUM | PBGPU_VERIFY_TOT_LEN, &bad, &first_bad)) != 0)
+                {
+                    fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, w->gpu,
+                            pbgpu_strerror(rc));
+                    last_error = rc;
+                    break;
+                }
+                if (bad)
+                {
+                    __atomic_add_fetch(&verified_bad[w->seq_idx], bad, __ATOMIC_RELAXED);
+                    pb_verify_failed_msg(seq_num, bad, first_bad,
+                                         (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch);
+                    last_error = PBGPU_EIO;
+                    verify_failed[w->seq_idx] = 1;
+                    break;
+                }
+            }
+        }
+        void *const bf = frg ? ffr[cur] : fr[cur]; /* the batch as it is encapsulated or landed */
         if (enc)
         {
-            if ((rc = B->encap(ctx, fr[cur], &eopts, efr[cur])) != 0)
+            if ((rc = B->encap(ctx, bf, &eopts, efr[cur])) != 0)
             {
                 fprintf(stderr, "[%d] Error encapsulating frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
                 last_error = rc;
@@ -715,7 +807,7 @@ static void *gpu_worker(void *p)
                 }
             }
         }
-        void *const lf = enc ? efr[cur] : fr[cur]; /* what lands: its lengths are what the ring and the totals count */
+        void *const lf = enc ? efr[cur] : bf; /* what lands: its lengths are what the ring and the totals count */
         /* double buffering: the next batch builds on the GPU while this one lands */
         const uint64_t n_next = claim_iters(w->seq_idx, seq->max_pckts, batch, fpi);
         if (n_next &&
@@ -959,6 +1051,8 @@ out:
             B->free_frames(ctx, fr[i]);
         if (efr[i])
             B->free_frames(ctx, efr[i]);
+        if (ffr[i])
+            B->free_frames(ctx, ffr[i]);
     }
     if (ctx)
         B->close(ctx);
@@ -1003,6 +1097,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     if (encap_on && (builder->encap == NULL || builder->alloc_encap == NULL))
     {
         fprintf(stderr, "[%d] --encap: this frame builder cannot encapsulate.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
+    }
+    if (frag_on && (builder->fragment == NULL || builder->alloc_frag == NULL))
+    {
+        fprintf(stderr, "[%d] --fragment: this frame builder cannot fragment.\n", seq_cnt + 1);
         last_error = PBGPU_ENOTSUP;
         return;
     }

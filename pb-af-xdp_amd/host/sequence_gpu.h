@@ -48,6 +48,11 @@ void pb_set_verbose(int verbose);
  * source port hashed.  NULL: none (the default). */
 void pb_set_encap(const pbgpu_encap_opts *opts);
 const pbgpu_encap_opts *pb_get_encap(void);
+/* --fragment MTU[:ignoredf] (main_gpu.c's own option): every built batch is fragmented on the GPU
+ * (pbgpu_fragment) before it is verified again, encapsulated, landed or packed.  NULL: none (the
+ * default). */
+void pb_set_fragment(const pbgpu_frag_opts *opts);
+const pbgpu_frag_opts *pb_get_fragment(void);
 
 void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cmd_line_af_xdp cmd);
 /* sequence.c:779-824: stop and join the workers, print the end-of-run lines,
@@ -102,6 +107,14 @@ typedef struct pb_builder
      * lands and verifies like a built one.  NULL: --encap is refused. */
     int (*alloc_encap)(void *h, uint16_t seq_idx, uint64_t n_iter, uint32_t extra, void **frames, uint32_t *max_len);
     int (*encap)(void *h, void *src, const pbgpu_encap_opts *opts, void *dst);
+    /* --fragment: a buffer for the fragments of n_iter iterations' frames (pbgpu_fragment_bound's
+     * frames and bytes for the sequence's longest frame) with `extra` more bytes per fragment, and the
+     * longest frame a fragmented batch can hold; the built batch `src` fragmented into such a buffer
+     * (pbgpu_fragment), which then verifies, encapsulates and lands like a built one.  NULL:
+     * --fragment is refused. */
+    int (*alloc_frag)(void *h, uint16_t seq_idx, uint64_t n_iter, const pbgpu_frag_opts *opts, uint32_t extra,
+                      void **frames, uint32_t *max_len);
+    int (*fragment)(void *h, void *src, const pbgpu_frag_opts *opts, void *dst);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

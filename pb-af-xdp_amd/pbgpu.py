@@ -217,6 +217,35 @@ class EncapOpts(C.Structure):
         return o
 
 
+FRAG_IGNORE_DF = 1  # split frames whose DF bit is set too
+
+
+class FragOpts(C.Structure):
+    """pbgpu_frag_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("mtu", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class FragResult(C.Structure):
+    """pbgpu_frag_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_in", C.c_uint64),
+        ("n_out", C.c_uint64),
+        ("n_split", C.c_uint64),
+        ("n_df", C.c_uint64),
+        ("n_other", C.c_uint64),
+        ("out_bytes", C.c_uint64),
+        ("out_min_len", C.c_uint32),
+        ("out_max_len", C.c_uint32),
+        ("device_ms", C.c_double),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -375,6 +404,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                       C.POINTER(C.c_double)]),
         "pbgpu_encap_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(EncapOpts), U64P, U64P]),
         "pbgpu_encap": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(EncapOpts), FP, C.POINTER(C.c_double)]),
+        "pbgpu_fragment_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
+        "pbgpu_fragment_bound": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
+        "pbgpu_fragment": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), FP, C.POINTER(FragResult)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -522,6 +554,18 @@ class FrameBuffer:
         _check(self.ctx.lib.pbgpu_encap(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(ms)), "encap")
         return float(ms.value)
 
+    def fragment(self, dst: "FrameBuffer", first: int = 0, n: Optional[int] = None, mtu: int = 1500,
+                 ignore_df: bool = False) -> FragResult:
+        """Fragments frames [first, first + n) (n None: to the last frame) into dst so that no IPv4
+        packet exceeds mtu; dst is then a frames buffer like a built one.  Returns the FragResult."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        opts = FragOpts(mtu, FRAG_IGNORE_DF if ignore_df else 0, 0)
+        res = FragResult()
+        _check(self.ctx.lib.pbgpu_fragment(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(res)),
+               "fragment")
+        return res
+
     def free(self) -> None:
         if self.ptr is not None:
             self.ctx.lib.pbgpu_frames_free(self.ctx.h, self.ptr)
@@ -654,6 +698,24 @@ class GpuContext:
         _check(self.lib.pbgpu_encap_size(self.h, fb.ptr, first, n, C.byref(opts), C.byref(frames), C.byref(nbytes)),
                "encap_size")
         return int(frames.value), int(nbytes.value)
+
+    def _frag_sizes(self, fn, what: str, fb: "FrameBuffer", first: int, n: Optional[int], mtu: int, ignore_df: bool):
+        if n is None:
+            n = int(fb.f.n_frames) - first
+        opts = FragOpts(mtu, FRAG_IGNORE_DF if ignore_df else 0, 0)
+        frames, nbytes = C.c_uint64(), C.c_uint64()
+        _check(fn(self.h, fb.ptr, first, n, C.byref(opts), C.byref(frames), C.byref(nbytes)), what)
+        return int(frames.value), int(nbytes.value)
+
+    def fragment_size(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, mtu: int = 1500,
+                      ignore_df: bool = False):
+        """The exact (frames, bytes) FrameBuffer.fragment would write (count and scan passes only)."""
+        return self._frag_sizes(self.lib.pbgpu_fragment_size, "fragment_size", fb, first, n, mtu, ignore_df)
+
+    def fragment_bound(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, mtu: int = 1500,
+                       ignore_df: bool = False):
+        """An upper bound of (frames, bytes) from fb's longest frame, with no device work."""
+        return self._frag_sizes(self.lib.pbgpu_fragment_bound, "fragment_bound", fb, first, n, mtu, ignore_df)
 
     def kernel_name(self, idx: int) -> str:
         buf = C.create_string_buffer(96)
