@@ -1758,6 +1758,147 @@ static int materialize_offsets(pbgpu_ctx *ctx, const pbgpu_frames *f)
     return PBGPU_OK;
 }
 
+// ---- shared by the builds, the upload, verify and the repackers (pcap pack, encap, fragment) ----
+
+#define PBCHK(call)             \
+    do                          \
+    {                           \
+        const int r_ = (call);  \
+        if (r_ != PBGPU_OK)     \
+            return r_;          \
+    } while (0)
+
+// A timed stretch of the context's stream: begin takes a pair and records its start, stop records
+// its end, ms waits for the stream and reads the time. The pair is back in the pool from the
+// start, whatever follows: it is used only until the call that took it returns.
+static int timed_begin(pbgpu_ctx *ctx, timing_pair *tp)
+{
+    PBCHK(timed_pair(ctx, tp));
+    ctx->pool.push_back(*tp);
+    HIPCHK(hipEventRecord(tp->a, ctx->stream));
+    return PBGPU_OK;
+}
+
+static int timed_stop(pbgpu_ctx *ctx, const timing_pair &tp)
+{
+    HIPCHK(hipEventRecord(tp.b, ctx->stream));
+    return PBGPU_OK;
+}
+
+static int timed_ms(pbgpu_ctx *ctx, const timing_pair &tp, float *ms)
+{
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipEventElapsedTime(ms, tp.a, tp.b));
+    return PBGPU_OK;
+}
+
+// A grow-only device scratch buffer: at least `need` units (`bytes` for them) after this; no
+// buffer and no capacity when the allocation fails.
+static int scratch_reserve(void **ptr, uint64_t *cap, uint64_t need, size_t bytes)
+{
+    if (need <= *cap)
+        return PBGPU_OK;
+    if (*ptr)
+        (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    if (hipMalloc(ptr, bytes) != hipSuccess)
+        return PBGPU_ENOMEM;
+    *cap = need;
+    return PBGPU_OK;
+}
+
+// Pages per workgroup of a launch over 4-KiB pages: they grow with the launch (at least 16384
+// workgroups in a large one, 32 pages at the most), and further where the grid would pass 2^24.
+static int page_grid(uint64_t npages, uint32_t *per_out, uint32_t *grid)
+{
+    uint64_t per = npages / 16384;
+    per = per < 1 ? 1 : (per > 32 ? 32 : per);
+    if ((npages + per - 1) / per > (1ull << 24))
+        per = (npages + (1ull << 24) - 1) >> 24;
+    if (per > 0xFFFFFFFFull)
+        return PBGPU_EINVAL;
+    *per_out = (uint32_t)per;
+    *grid = (uint32_t)((npages + per - 1) / per);
+    return PBGPU_OK;
+}
+
+// Frames [first, first + n) of a buffer that holds frames (reserved: set by the first build or upload)
+static bool frames_range_ok(const pbgpu_frames *f, uint64_t first, uint64_t n)
+{
+    return f->reserved != NULL && first <= f->n_frames && n <= f->n_frames - first;
+}
+
+// The bytes of frames [first, first + n) and where they end in the buffer: from the fixed length,
+// or offsets[first + n] - offsets[first] read back (after materialising them).
+static int range_bytes(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, uint64_t *body,
+                       uint64_t *src_end)
+{
+    if (ctx == NULL || src == NULL || !frames_range_ok(src, first, n))
+        return PBGPU_EINVAL;
+    *body = 0;
+    *src_end = 0;
+    if (n == 0)
+        return PBGPU_OK;
+    if (src->fixed_len)
+    {
+        *body = n * src->fixed_len;
+        *src_end = (first + n) * src->fixed_len;
+        return PBGPU_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    PBCHK(materialize_offsets(ctx, src));
+    uint64_t o[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&o[0], src->offsets + first, sizeof o[0], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&o[1], src->offsets + first + n, sizeof o[1], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (o[1] < o[0])
+        return PBGPU_EIO;
+    *body = o[1] - o[0];
+    *src_end = o[1];
+    return PBGPU_OK;
+}
+
+// A repacker's source and destination must be apart: the allocations, the readers' 64-B slack included
+static bool buffers_overlap(const pbgpu_frames *src, const pbgpu_frames *dst)
+{
+    const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
+    const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
+    return s0 < d1 && d0 < s1;
+}
+
+// Taking a buffer over as the destination of a build, an upload or a repack on `st`: the work
+// follows the buffer's last writer on another stream, and the landings queued from the buffer (a
+// landing never reads frames being overwritten). The lengths are those of the frames to come.
+static int take_dst(pbgpu_frames *dst, hipStream_t st, uint32_t min_len, uint32_t max_len, uint32_t up_max_len1,
+                    frames_events **fe_out)
+{
+    frames_events *fe = frames_ev(dst);
+    if (fe == NULL)
+        return PBGPU_ENOMEM;
+    if (fe->last && fe->last != st)
+    {
+        if (fe->moved == nullptr)
+            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fe->moved, fe->last));
+        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
+    }
+    fe->last = st;
+    fe->packed32 = false;
+    fe->up_max_len1 = up_max_len1;
+    fe->min_len = min_len;
+    fe->max_len = max_len;
+    if (fe->land_pending)
+    {
+        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
+        fe->land_pending = false;
+    }
+    if (fe_out)
+        *fe_out = fe;
+    return PBGPU_OK;
+}
+
 int pbgpu_frames_offsets(pbgpu_ctx *ctx, pbgpu_frames *f)
 {
     if (ctx == NULL || f == NULL)
@@ -1825,28 +1966,8 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
             HIPCHK(hipStreamCreateWithFlags(&ctx->seq_stream[si], hipStreamNonBlocking));
         st = ctx->seq_stream[si];
     }
-    frames_events *fe = frames_ev(out);
-    if (fe == NULL)
-        return PBGPU_ENOMEM;
-    // a buffer last built on another stream: this build follows that one
-    if (fe->last && fe->last != st)
-    {
-        if (fe->moved == nullptr)
-            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fe->moved, fe->last));
-        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
-    }
-    fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = 0;
-    fe->min_len = S.min_flen;
-    fe->max_len = S.max_flen;
-    // a landing queued from this buffer must have read it before the build overwrites it
-    if (fe->land_pending)
-    {
-        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
-        fe->land_pending = false;
-    }
+    frames_events *fe = nullptr;
+    PBCHK(take_dst(out, st, S.min_flen, S.max_flen, 0, &fe));
     pb_kargs K = S.K;
     K.first_iter = first_iter;
     K.n_frames = nf;
@@ -2283,10 +2404,9 @@ static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint6
         const uint64_t b0 = first * f->fixed_len, b1 = (first + n) * f->fixed_len;
         A->page0 = b0 >> 12;
         A->npages = ((b1 - 1) >> 12) - A->page0 + 1;
-        uint64_t per = A->npages / 16384; // pages per wave: at least 16384 waves in a large launch
-        per = per < 1 ? 1 : (per > 32 ? 32 : per);
-        A->wgf = (uint32_t)per;
-        *grid = (uint32_t)((A->npages + per - 1) / per);
+        // pages per wave. n <= n_frames < 2^32 of at most 128 B: npages <= 2^27 + 1, far from
+        // page_grid's grid cap and its refusal
+        (void)page_grid(A->npages, &A->wgf, grid);
         return 0;
     }
     const int G = mean <= 192 ? 8 : (mean <= 768 ? 16 : (mean <= 3072 ? 32 : 64));
@@ -2307,9 +2427,7 @@ static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint6
 int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, uint32_t checks,
                  pbgpu_verify_result *res, uint8_t *codes_out)
 {
-    if (ctx == NULL || f == NULL || res == NULL || f->reserved == NULL) // reserved: set by the first build or upload
-        return PBGPU_EINVAL;
-    if (first_frame > f->n_frames || n > f->n_frames - first_frame)
+    if (ctx == NULL || f == NULL || res == NULL || !frames_range_ok(f, first_frame, n))
         return PBGPU_EINVAL;
     memset(res, 0, sizeof *res);
     res->first_bad = UINT64_MAX;
@@ -2348,50 +2466,27 @@ int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t
     A.checks = checks & PBGPU_VERIFY_ALL;
     uint32_t grid = 0;
     const int shape = verify_shape(f, first_frame, n, mean, &A, &grid);
-    if (grid > ctx->vfy_rec_cap)
-    {
-        if (ctx->d_vfy_rec)
-            (void)hipFree(ctx->d_vfy_rec);
-        ctx->d_vfy_rec = nullptr;
-        ctx->vfy_rec_cap = 0;
-        if (hipMalloc((void **)&ctx->d_vfy_rec, (size_t)grid * PB_VREC_DW * sizeof(uint32_t)) != hipSuccess)
-            return PBGPU_ENOMEM;
-        ctx->vfy_rec_cap = grid;
-    }
+    PBCHK(scratch_reserve((void **)&ctx->d_vfy_rec, &ctx->vfy_rec_cap, grid,
+                          (size_t)grid * PB_VREC_DW * sizeof(uint32_t)));
     if (ctx->h_vres == nullptr)
     {
         HIPCHK(hipHostMalloc((void **)&ctx->h_vres, 8 * sizeof(unsigned long long),
                              hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_vres, ctx->h_vres, 0));
     }
-    if (codes_out && n > ctx->vcodes_cap)
-    {
-        if (ctx->d_vcodes)
-            (void)hipFree(ctx->d_vcodes);
-        ctx->d_vcodes = nullptr;
-        ctx->vcodes_cap = 0;
-        if (hipMalloc((void **)&ctx->d_vcodes, n) != hipSuccess)
-            return PBGPU_ENOMEM;
-        ctx->vcodes_cap = n;
-    }
+    if (codes_out)
+        PBCHK(scratch_reserve((void **)&ctx->d_vcodes, &ctx->vcodes_cap, n, n));
     A.rec = ctx->d_vfy_rec;
     A.codes = codes_out ? ctx->d_vcodes : nullptr;
     timing_pair tp;
-    {
-        const int prc = timed_pair(ctx, &tp);
-        if (prc != PBGPU_OK)
-            return prc;
-    }
-    ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
-    HIPCHK(hipEventRecord(tp.a, ctx->stream));
+    PBCHK(timed_begin(ctx, &tp));
     HIPCHK(pbk_launch_verify(&A, shape, grid, ctx->stream));
     HIPCHK(pbk_launch_vfold(ctx->d_vfy_rec, grid, ctx->d_vres, ctx->stream));
-    HIPCHK(hipEventRecord(tp.b, ctx->stream));
-    if (codes_out)
+    PBCHK(timed_stop(ctx, tp));
+    if (codes_out) // after the timed stretch
         HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+    PBCHK(timed_ms(ctx, tp, &ms));
     res->n_bad = ctx->h_vres[0];
     res->bad_short = ctx->h_vres[1];
     res->bad_ip_csum = ctx->h_vres[2];
@@ -2435,28 +2530,8 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
         return PBGPU_ENOSPC;
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
-    frames_events *fe = frames_ev(f);
-    if (fe == NULL)
-        return PBGPU_ENOMEM;
-    // as a build: after the buffer's last build on another stream and the landings queued from it
     hipStream_t st = ctx->stream;
-    if (fe->last && fe->last != st)
-    {
-        if (fe->moved == nullptr)
-            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fe->moved, fe->last));
-        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
-    }
-    fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = host_offsets ? (uint32_t)max_len + 1 : 0;
-    fe->min_len = (uint32_t)min_len;
-    fe->max_len = (uint32_t)max_len;
-    if (fe->land_pending)
-    {
-        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
-        fe->land_pending = false;
-    }
+    PBCHK(take_dst(f, st, (uint32_t)min_len, (uint32_t)max_len, host_offsets ? (uint32_t)max_len + 1 : 0, nullptr));
     if (total)
         HIPCHK(hipMemcpyAsync(f->data, host_data, total, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> off;
@@ -2514,52 +2589,15 @@ int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_
 
 // ---- pcap stream packing ----
 
-// Argument checks shared by pbgpu_pcap_size and pbgpu_pcap_pack, then the frames' bytes: from the
-// fixed length, or offsets[first + n] - offsets[first] read back (after materialising them).
-static int pcap_body(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, uint32_t flags, uint64_t *body,
-                     uint64_t *src_end)
-{
-    if (ctx == NULL || src == NULL || src->reserved == NULL) // reserved: set by the first build or upload
-        return PBGPU_EINVAL;
-    if (flags & ~(PBGPU_PCAP_FILE_HEADER | PBGPU_PCAP_NSEC))
-        return PBGPU_EINVAL;
-    if (first > src->n_frames || n > src->n_frames - first)
-        return PBGPU_EINVAL;
-    *body = 0;
-    *src_end = 0;
-    if (n == 0)
-        return PBGPU_OK;
-    if (src->fixed_len)
-    {
-        *body = n * src->fixed_len;
-        *src_end = (first + n) * src->fixed_len;
-        return PBGPU_OK;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    const int mrc = materialize_offsets(ctx, src);
-    if (mrc != PBGPU_OK)
-        return mrc;
-    uint64_t o[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&o[0], src->offsets + first, sizeof o[0], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&o[1], src->offsets + first + n, sizeof o[1], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (o[1] < o[0])
-        return PBGPU_EIO;
-    *body = o[1] - o[0];
-    *src_end = o[1];
-    return PBGPU_OK;
-}
+#define PB_PCAP_FLAGS (PBGPU_PCAP_FILE_HEADER | PBGPU_PCAP_NSEC)
 
 int pbgpu_pcap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, uint32_t flags,
                     uint64_t *nbytes)
 {
-    if (nbytes == NULL)
+    if (nbytes == NULL || (flags & ~PB_PCAP_FLAGS))
         return PBGPU_EINVAL;
     uint64_t body = 0, src_end = 0;
-    const int rc = pcap_body(ctx, src, first_frame, n, flags, &body, &src_end);
-    if (rc != PBGPU_OK)
-        return rc;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
     *nbytes = ((flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u) + 16u * n + body;
     return PBGPU_OK;
 }
@@ -2569,15 +2607,10 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL || nbytes == NULL || opts->reserved != 0)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL)
+    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
         return PBGPU_EINVAL;
-    {
-        // the allocations, the readers' 64-B slack included
-        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
-        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
-        if (s0 < d1 && d0 < s1)
-            return PBGPU_EINVAL;
-    }
+    if (opts->flags & ~PB_PCAP_FLAGS)
+        return PBGPU_EINVAL;
     if (n)
     {
         // the device computes (first_index + j) * step_ps and t0_ns + that / 1000 in 64 bits
@@ -2590,9 +2623,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
             return PBGPU_EINVAL;
     }
     uint64_t body = 0, src_end = 0;
-    const int brc = pcap_body(ctx, src, first_frame, n, opts->flags, &body, &src_end);
-    if (brc != PBGPU_OK)
-        return brc;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
     if (src_end > src->capacity_bytes)
         return PBGPU_EINVAL;
     const uint32_t H = (opts->flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u;
@@ -2602,27 +2633,8 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
         return PBGPU_ENOSPC;
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
-    frames_events *fe = frames_ev(dst);
-    if (fe == NULL)
-        return PBGPU_ENOMEM;
-    // as an upload: after dst's last build on another stream and the landings queued from it
     hipStream_t st = ctx->stream;
-    if (fe->last && fe->last != st)
-    {
-        if (fe->moved == nullptr)
-            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fe->moved, fe->last));
-        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
-    }
-    fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = 0;
-    fe->min_len = fe->max_len = 0;
-    if (fe->land_pending)
-    {
-        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
-        fe->land_pending = false;
-    }
+    PBCHK(take_dst(dst, st, 0, 0, 0, nullptr)); // a byte stream: no frames, so no lengths
     dst->first_iter = 0;
     dst->n_frames = 0;
     dst->fixed_len = 0;
@@ -2645,29 +2657,13 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
         A.t0_ns = opts->t0_ns;
         A.step_ps = opts->step_ps;
         A.first_index = opts->first_index;
-        // pages per workgroup grow with the launch: at least 16384 workgroups in a large one, and a
-        // grid below 2^24 however long the stream
-        const uint64_t npages = (end16 + 4095) >> 12;
-        uint64_t per = npages / 16384;
-        per = per < 1 ? 1 : (per > 32 ? 32 : per);
-        if ((npages + per - 1) / per > (1ull << 24))
-            per = (npages + (1ull << 24) - 1) >> 24;
-        if (per > 0xFFFFFFFFull)
-            return PBGPU_EINVAL;
-        A.per = (uint32_t)per;
-        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        uint32_t grid = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
         timing_pair tp;
-        {
-            const int prc = timed_pair(ctx, &tp);
-            if (prc != PBGPU_OK)
-                return prc;
-        }
-        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
-        HIPCHK(hipEventRecord(tp.a, st));
+        PBCHK(timed_begin(ctx, &tp));
         HIPCHK(pbk_launch_pcap(&A, grid, st));
-        HIPCHK(hipEventRecord(tp.b, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &ms));
     }
     *nbytes = total;
     if (device_ms)
@@ -2678,7 +2674,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
 // ---- encapsulation ----
 
 // Argument checks shared by pbgpu_encap_size and pbgpu_encap, then the header's size and the
-// frames' bytes (pcap_body).
+// frames' bytes (range_bytes).
 static int encap_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_encap_opts *opts,
                        uint32_t *P, uint64_t *body, uint64_t *src_end)
 {
@@ -2692,7 +2688,7 @@ static int encap_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64
     const frames_events *fs = (const frames_events *)src->reserved;
     if (src->n_frames && (fs->min_len < 14u || fs->max_len > 65535u - *P))
         return PBGPU_EINVAL;
-    return pcap_body(ctx, src, first, n, 0, body, src_end);
+    return range_bytes(ctx, src, first, n, body, src_end);
 }
 
 int pbgpu_encap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
@@ -2702,9 +2698,7 @@ int pbgpu_encap_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, ui
         return PBGPU_EINVAL;
     uint32_t P = 0;
     uint64_t body = 0, src_end = 0;
-    const int rc = encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end);
-    if (rc != PBGPU_OK)
-        return rc;
+    PBCHK(encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end));
     *frames = n;
     *bytes = body + n * P;
     return PBGPU_OK;
@@ -2715,20 +2709,11 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL)
+    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
         return PBGPU_EINVAL;
-    {
-        // the allocations, the readers' 64-B slack included
-        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
-        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
-        if (s0 < d1 && d0 < s1)
-            return PBGPU_EINVAL;
-    }
     uint32_t P = 0;
     uint64_t body = 0, src_end = 0;
-    const int brc = encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end);
-    if (brc != PBGPU_OK)
-        return brc;
+    PBCHK(encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end));
     if (src_end > src->capacity_bytes)
         return PBGPU_EINVAL;
     const uint64_t total = body + n * P;
@@ -2737,30 +2722,11 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
         return PBGPU_ENOSPC;
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
-    frames_events *fe = frames_ev(dst);
-    if (fe == NULL)
-        return PBGPU_ENOMEM;
     const frames_events *fs = (const frames_events *)src->reserved;
     const uint32_t src_min = fs->min_len, src_max = fs->max_len;
-    // as an upload: after dst's last build on another stream and the landings queued from it
     hipStream_t st = ctx->stream;
-    if (fe->last && fe->last != st)
-    {
-        if (fe->moved == nullptr)
-            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fe->moved, fe->last));
-        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
-    }
-    fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = (n && !src->fixed_len) ? src_max + P + 1 : 0;
-    fe->min_len = n ? src_min + P : 0;
-    fe->max_len = n ? src_max + P : 0;
-    if (fe->land_pending)
-    {
-        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
-        fe->land_pending = false;
-    }
+    PBCHK(take_dst(dst, st, n ? src_min + P : 0, n ? src_max + P : 0, (n && !src->fixed_len) ? src_max + P + 1 : 0,
+                   nullptr));
     float ms = 0;
     if (n)
     {
@@ -2820,29 +2786,13 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
         for (uint32_t i = 0; i < PB_EN_TDW; ++i)
             A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
                        ((uint32_t)t[4 * i + 3] << 24);
-        // pages per workgroup as pbgpu_pcap_pack: at least 16384 workgroups in a large launch, and a
-        // grid below 2^24 however long the output
-        const uint64_t npages = (end16 + 4095) >> 12;
-        uint64_t per = npages / 16384;
-        per = per < 1 ? 1 : (per > 32 ? 32 : per);
-        if ((npages + per - 1) / per > (1ull << 24))
-            per = (npages + (1ull << 24) - 1) >> 24;
-        if (per > 0xFFFFFFFFull)
-            return PBGPU_EINVAL;
-        A.per = (uint32_t)per;
-        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        uint32_t grid = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
         timing_pair tp;
-        {
-            const int prc = timed_pair(ctx, &tp);
-            if (prc != PBGPU_OK)
-                return prc;
-        }
-        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
-        HIPCHK(hipEventRecord(tp.a, st));
+        PBCHK(timed_begin(ctx, &tp));
         HIPCHK(pbk_launch_encap(&A, grid, st)); // variable length: dst->offsets by a launch of its own first
-        HIPCHK(hipEventRecord(tp.b, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &ms));
     }
     dst->first_iter = 0;
     dst->n_frames = n;
@@ -2858,11 +2808,11 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
 // Argument checks shared by the three calls; nothing on the device.
 static int frag_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts)
 {
-    if (ctx == NULL || src == NULL || opts == NULL || src->reserved == NULL)
+    if (ctx == NULL || src == NULL || opts == NULL)
         return PBGPU_EINVAL;
     if (opts->mtu < 68u || opts->mtu > 65535u || (opts->flags & ~PBGPU_FRAG_IGNORE_DF) || opts->reserved != 0)
         return PBGPU_EINVAL;
-    if (first > src->n_frames || n > src->n_frames - first)
+    if (!frames_range_ok(src, first, n))
         return PBGPU_EINVAL;
     const frames_events *fs = (const frames_events *)src->reserved;
     if (src->n_frames && fs->min_len < 14u)
@@ -2891,16 +2841,7 @@ static int frag_count(pbgpu_ctx *ctx, pb_fgargs *A, unsigned long long *res)
     const uint64_t nblk = (A->n + PB_FG_WT - 1u) / PB_FG_WT;
     if (nblk > 0xFFFFFFFFull)
         return PBGPU_EINVAL;
-    if (A->n > ctx->fg_cnt_cap)
-    {
-        if (ctx->d_fg_cnt)
-            (void)hipFree(ctx->d_fg_cnt);
-        ctx->d_fg_cnt = nullptr;
-        ctx->fg_cnt_cap = 0;
-        if (hipMalloc((void **)&ctx->d_fg_cnt, PB_FG_RES_DW * 8u + nblk * 8u + A->n * 4u) != hipSuccess)
-            return PBGPU_ENOMEM;
-        ctx->fg_cnt_cap = A->n;
-    }
+    PBCHK(scratch_reserve((void **)&ctx->d_fg_cnt, &ctx->fg_cnt_cap, A->n, PB_FG_RES_DW * 8u + nblk * 8u + A->n * 4u));
     A->res = (unsigned long long *)ctx->d_fg_cnt;
     A->bsum = A->res + PB_FG_RES_DW;
     A->kcnt = (uint32_t *)(A->bsum + nblk);
@@ -2914,9 +2855,7 @@ int pbgpu_fragment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame
 {
     if (frames == NULL || bytes == NULL)
         return PBGPU_EINVAL;
-    const int rc = frag_check(ctx, src, first_frame, n, opts);
-    if (rc != PBGPU_OK)
-        return rc;
+    PBCHK(frag_check(ctx, src, first_frame, n, opts));
     const frames_events *fs = (const frames_events *)src->reserved;
     const uint64_t C = (opts->mtu - 20u) & ~7u, max_len = fs->max_len;
     uint64_t kmax = 1;
@@ -2932,13 +2871,9 @@ int pbgpu_fragment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame,
 {
     if (frames == NULL || bytes == NULL)
         return PBGPU_EINVAL;
-    const int rc = frag_check(ctx, src, first_frame, n, opts);
-    if (rc != PBGPU_OK)
-        return rc;
+    PBCHK(frag_check(ctx, src, first_frame, n, opts));
     uint64_t body = 0, src_end = 0;
-    const int brc = pcap_body(ctx, src, first_frame, n, 0, &body, &src_end);
-    if (brc != PBGPU_OK)
-        return brc;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
     *frames = n;
     *bytes = body;
     const frames_events *fs = (const frames_events *)src->reserved;
@@ -2949,9 +2884,7 @@ int pbgpu_fragment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame,
     pb_fgargs A;
     frag_args(&A, src, first_frame, n, opts);
     unsigned long long r[PB_FG_RES_DW];
-    const int crc = frag_count(ctx, &A, r);
-    if (crc != PBGPU_OK)
-        return crc;
+    PBCHK(frag_count(ctx, &A, r));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (r[0] < n)
         return PBGPU_EIO;
@@ -2965,22 +2898,11 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL)
+    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
         return PBGPU_EINVAL;
-    {
-        // the allocations, the readers' 64-B slack included
-        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + src->capacity_bytes + 64;
-        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + dst->capacity_bytes + 64;
-        if (s0 < d1 && d0 < s1)
-            return PBGPU_EINVAL;
-    }
-    const int rc = frag_check(ctx, src, first_frame, n, opts);
-    if (rc != PBGPU_OK)
-        return rc;
+    PBCHK(frag_check(ctx, src, first_frame, n, opts));
     uint64_t body = 0, src_end = 0;
-    const int brc = pcap_body(ctx, src, first_frame, n, 0, &body, &src_end);
-    if (brc != PBGPU_OK)
-        return brc;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
     if (src_end > src->capacity_bytes)
         return PBGPU_EINVAL;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2994,17 +2916,11 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
     timing_pair tp = {nullptr, nullptr};
     if (n)
     {
-        const int prc = timed_pair(ctx, &tp);
-        if (prc != PBGPU_OK)
-            return prc;
-        ctx->pool.push_back(tp); // back in the pool whatever follows; used here until this call returns
-        HIPCHK(hipEventRecord(tp.a, st));
+        PBCHK(timed_begin(ctx, &tp)); // the timed stretch: count, scan, map and writer
         if (!copy)
         {
             // the count and scan run, and their result is read, before anything of dst is touched
-            const int crc = frag_count(ctx, &A, r);
-            if (crc != PBGPU_OK)
-                return crc;
+            PBCHK(frag_count(ctx, &A, r));
             HIPCHK(hipStreamSynchronize(st));
             if (r[0] < n)
                 return PBGPU_EIO;
@@ -3015,37 +2931,11 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
     const uint64_t end16 = (total + 15) & ~15ull;
     if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
         return PBGPU_ENOSPC;
-    if (n && !copy && n_out > ctx->fg_map_cap)
-    {
-        if (ctx->d_fg_map)
-            (void)hipFree(ctx->d_fg_map);
-        ctx->d_fg_map = nullptr;
-        ctx->fg_map_cap = 0;
-        if (hipMalloc((void **)&ctx->d_fg_map, n_out * sizeof(uint64_t)) != hipSuccess)
-            return PBGPU_ENOMEM;
-        ctx->fg_map_cap = n_out;
-    }
-    frames_events *fe = frames_ev(dst);
-    if (fe == NULL)
-        return PBGPU_ENOMEM;
-    // as an upload: after dst's last build on another stream and the landings queued from it
-    if (fe->last && fe->last != st)
-    {
-        if (fe->moved == nullptr)
-            HIPCHK(hipEventCreateWithFlags(&fe->moved, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fe->moved, fe->last));
-        HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
-    }
-    fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = (n && !copy) ? (uint32_t)r[5] + 1u : 0;
-    fe->min_len = n ? (uint32_t)r[4] : 0;
-    fe->max_len = n ? (uint32_t)r[5] : 0;
-    if (fe->land_pending)
-    {
-        HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
-        fe->land_pending = false;
-    }
+    if (n && !copy)
+        PBCHK(scratch_reserve((void **)&ctx->d_fg_map, &ctx->fg_map_cap, n_out, n_out * sizeof(uint64_t)));
+    frames_events *fe = nullptr;
+    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, (n && !copy) ? (uint32_t)r[5] + 1u : 0,
+                   &fe));
     float ms = 0;
     if (n)
     {
@@ -3055,20 +2945,11 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
         A.n_out = n_out;
         A.total = total;
         A.end16 = end16;
-        // pages per workgroup as pbgpu_encap
-        const uint64_t npages = (end16 + 4095) >> 12;
-        uint64_t per = npages / 16384;
-        per = per < 1 ? 1 : (per > 32 ? 32 : per);
-        if ((npages + per - 1) / per > (1ull << 24))
-            per = (npages + (1ull << 24) - 1) >> 24;
-        if (per > 0xFFFFFFFFull)
-            return PBGPU_EINVAL;
-        A.per = (uint32_t)per;
-        const uint32_t grid = (uint32_t)((npages + per - 1) / per);
+        uint32_t grid = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
         HIPCHK(pbk_launch_frag(&A, copy ? 2 : 1, grid, st));
-        HIPCHK(hipEventRecord(tp.b, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, tp.a, tp.b));
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &ms));
     }
     dst->first_iter = 0;
     dst->n_frames = n_out;

@@ -4273,6 +4273,131 @@ extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t 
     return hipGetLastError();
 }
 
+// ---------------- repack helpers (pcap pack, encap, fragment: DESIGN.md 5.9-5.11) ----------------
+// The three writers are destination-owned: a workgroup owns consecutive 4-KiB pages of the output, a
+// lane one aligned 16-B chunk of a page per step.  Output record j is source frame first + j with
+// `add` bytes inserted (pcap: a 16-B record header, encap: P header bytes); variable length keeps a
+// window s_rel[] of record positions in LDS, relative to its first record, 0xFFFFFFFF past the end.
+
+// the last k in [lo, hi] with s_rel[k] <= d (lo itself where there is none)
+__device__ __forceinline__ uint32_t pb_rp_find(const uint32_t *s_rel, uint32_t d, uint32_t lo, uint32_t hi)
+{
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (s_rel[mid] <= d)
+            lo = mid;
+        else
+            hi = mid - 1u;
+    }
+    return lo;
+}
+
+// bytes b of the dword at offset o with o + b < bound, as a byte mask
+__device__ __forceinline__ uint32_t pb_rp_lt(int32_t o, int32_t bound)
+{
+    const int32_t k = bound - o;
+    return k <= 0 ? 0u : (k >= 4 ? 0xFFFFFFFFu : (1u << (8u * (uint32_t)k)) - 1u);
+}
+
+// source bytes [a, a + 16) as four dwords, of which bytes [lo, hi) of the 16 are wanted (the rest
+// unspecified): aligned dwords, loaded only if they hold a wanted byte, moved by v_alignbyte
+__device__ __forceinline__ void pb_rp_gather(const uint32_t *w, int64_t a, int32_t lo, int32_t hi, uint32_t out[4])
+{
+    const int64_t i = a >> 2; // floor: a is negative only where nothing before byte 0 is wanted
+    const uint32_t sh = (uint32_t)a & 3u;
+    uint32_t d[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+    {
+        const int32_t b = 4 * t - (int32_t)sh; // the dword's first byte among the 16
+        d[t] = (b + 4 > lo && b < hi) ? w[i + t] : 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        out[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
+}
+
+// source bytes [a, a + 16), all wanted: four aligned dwords and, off alignment, a fifth, which
+// then still holds one of the bytes
+__device__ __forceinline__ pb_u32x4 pb_rp_copy16(const uint32_t *w, uint64_t a)
+{
+    const uint64_t i = a >> 2;
+    const uint32_t sh = (uint32_t)a & 3u;
+    const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
+    const uint32_t w4 = sh ? w[i + 4] : 0u;
+    pb_u32x4 v;
+    v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
+    v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+    v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
+    v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+    return v;
+}
+
+// A header T, the first ndw <= N dwords of it, moved to the alignment it has in the output (its
+// first byte sh bytes into an aligned dword): staged dword u is output bytes hb + 4u .. + 3, hb the
+// header's first byte rounded down to 4
+template <uint32_t N>
+__device__ __forceinline__ void pb_rp_stage(uint32_t *slot, const uint32_t (&T)[N], uint32_t ndw, uint32_t sh)
+{
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u)
+        if (u < ndw)
+            slot[u] = sh ? __builtin_amdgcn_alignbyte(T[u], u ? T[u - 1u] : 0u, 4u - sh) : T[u];
+}
+
+// j0: the record holding output byte q > 0 (counted from record 0's first byte), g0: that record's
+// first byte.  Variable length: add j + offsets[first + j] rises with j, the last j in [0, n] at or
+// below q; fixed length: the one 64-bit division, once per workgroup
+template <bool VAR>
+__device__ __forceinline__ void pb_rp_first(const uint64_t *offsets, uint64_t first, uint64_t n, uint32_t add,
+                                            uint32_t reclen, uint64_t q, uint64_t &j0, uint64_t &g0)
+{
+    if (VAR)
+    {
+        const uint64_t ob = offsets[first];
+        uint64_t lo = 0, hi = n;
+        while (lo < hi)
+        {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if ((uint64_t)add * mid + (offsets[first + mid] - ob) <= q)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        j0 = lo;
+        g0 = (uint64_t)add * lo + (offsets[first + lo] - ob);
+    }
+    else
+    {
+        j0 = q / reclen;
+        g0 = j0 * reclen;
+    }
+}
+
+// The window moves to record j0, by all wt lanes between two barriers of the caller's; returns
+// frame first + j0's offset in src
+__device__ __forceinline__ uint64_t pb_rp_refill(uint32_t *s_rel, uint32_t win, uint32_t wt, const uint64_t *offsets,
+                                                 uint64_t first, uint64_t n, uint32_t add, uint64_t j0)
+{
+    const uint64_t offj0 = offsets[first + (j0 < n ? j0 : n)];
+    for (uint32_t k = threadIdx.x; k < win; k += wt)
+    {
+        const uint64_t jj = j0 + k;
+        s_rel[k] = jj <= n ? add * k + (uint32_t)(offsets[first + jj] - offj0) : 0xFFFFFFFFu;
+    }
+    return offj0;
+}
+
+// Fixed length: the next page's first byte is 4096 on, a whole number of records and d0 bytes
+__device__ __forceinline__ void pb_rp_next_page(int32_t &d0, uint64_t &j0, const pb_div &rec, uint32_t reclen)
+{
+    const int32_t dn = d0 + 4096;
+    const uint32_t kn = pb_divq((uint32_t)dn, rec);
+    d0 = dn - (int32_t)(kn * reclen);
+    j0 += kn;
+}
+
 // ---------------- pcap stream packing (pbgpu_pcap_pack) ----------------
 // The stream: the 24-B pcap file header (optional), then per frame a 16-B record header
 // {ts_sec, ts_frac, len, len} and the frame's bytes.  Destination-owned: a workgroup owns `per`
@@ -4366,30 +4491,8 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
     // d0: that byte's offset in the record
     const int64_t q0 = (int64_t)p - (int64_t)A.hdr;
     uint64_t j0 = 0, g0 = 0;
-    const uint64_t ob = VAR ? A.offsets[A.first] : 0;
     if (q0 > 0)
-    {
-        if (VAR)
-        {
-            // 16 j + offsets[first + j] rises with j: the last j in [0, n] at or below q0
-            uint64_t lo = 0, hi = A.n;
-            while (lo < hi)
-            {
-                const uint64_t mid = lo + (hi - lo + 1) / 2;
-                if (16u * mid + (A.offsets[A.first + mid] - ob) <= (uint64_t)q0)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
-            j0 = lo;
-            g0 = 16u * lo + (A.offsets[A.first + lo] - ob);
-        }
-        else
-        {
-            j0 = (uint64_t)q0 / reclen; // the one 64-bit division, once per workgroup
-            g0 = j0 * reclen;
-        }
-    }
+        pb_rp_first<VAR>(A.offsets, A.first, A.n, 16u, reclen, (uint64_t)q0, j0, g0);
     int32_t d0 = (int32_t)(q0 - (int64_t)g0);
     uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
     bool have_win = false;
@@ -4402,25 +4505,12 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
         {
             if (have_win) // d0 >= 4096 - 24 here, and inside the window
             {
-                uint32_t lo = 0, hi = PB_PC_WIN - 1u;
-                while (lo < hi)
-                {
-                    const uint32_t mid = (lo + hi + 1u) >> 1;
-                    if (s_rel[mid] <= (uint32_t)d0)
-                        lo = mid;
-                    else
-                        hi = mid - 1u;
-                }
+                const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_PC_WIN - 1u);
                 j0 += lo;
                 d0 -= (int32_t)s_rel[lo];
             }
             __syncthreads(); // the window's readers are done
-            offj0 = A.offsets[A.first + (j0 < A.n ? j0 : A.n)];
-            for (uint32_t k = tid; k < PB_PC_WIN; k += PB_PC_WT)
-            {
-                const uint64_t jj = j0 + k;
-                s_rel[k] = jj <= A.n ? 16u * k + (uint32_t)(A.offsets[A.first + jj] - offj0) : 0xFFFFFFFFu;
-            }
+            offj0 = pb_rp_refill(s_rel, PB_PC_WIN, PB_PC_WT, A.offsets, A.first, A.n, 16u, j0);
             __syncthreads();
             have_win = true;
         }
@@ -4435,16 +4525,7 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
             {
                 if (VAR)
                 {
-                    uint32_t lo = 0, hi = PB_PC_WIN - 1u;
-                    while (lo < hi)
-                    {
-                        const uint32_t mid = (lo + hi + 1u) >> 1;
-                        if (s_rel[mid] <= (uint32_t)d)
-                            lo = mid;
-                        else
-                            hi = mid - 1u;
-                    }
-                    k = lo;
+                    k = pb_rp_find(s_rel, (uint32_t)d, 0u, PB_PC_WIN - 1u);
                     r = d - (int32_t)s_rel[k];
                 }
                 else
@@ -4480,17 +4561,8 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
             pb_u32x4 v;
             if (r >= 16 && r + 16 <= ea)
             {
-                // wholly inside the frame's bytes: four aligned dwords and, off alignment, a fifth,
-                // which still holds a byte of the frame
-                const uint64_t a = Ra.off + (uint32_t)(r - 16);
-                const uint64_t i = a >> 2;
-                const uint32_t sh = (uint32_t)a & 3u;
-                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
-                const uint32_t w4 = sh ? w[i + 4] : 0u;
-                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
-                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+                // wholly inside the frame's bytes (so a fifth dword still holds a byte of the frame)
+                v = pb_rp_copy16(w, Ra.off + (uint32_t)(r - 16));
             }
             else
             {
@@ -4537,12 +4609,7 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
         if (VAR)
             d0 += 4096;
         else
-        {
-            const int32_t dn = d0 + 4096;
-            const uint32_t kn = pb_divq((uint32_t)dn, A.rec);
-            d0 = dn - (int32_t)(kn * reclen);
-            j0 += kn;
-        }
+            pb_rp_next_page(d0, j0, A.rec, reclen);
     }
 }
 
@@ -4568,46 +4635,6 @@ extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStre
 // headers, and three byte masks per dword that select among them.  A wave none of whose chunks
 // touches a header takes a plain shifted copy instead; the choice is per wave, never per lane.
 
-// bytes b of the dword at offset o with o + b < bound, as a byte mask
-__device__ __forceinline__ uint32_t pb_en_lt(int32_t o, int32_t bound)
-{
-    const int32_t k = bound - o;
-    return k <= 0 ? 0u : (k >= 4 ? 0xFFFFFFFFu : (1u << (8u * (uint32_t)k)) - 1u);
-}
-
-// source bytes [a, a + 16) as four dwords, of which bytes [lo, hi) of the 16 are wanted (the rest
-// unspecified): aligned dwords, loaded only if they hold a wanted byte, moved by v_alignbyte
-__device__ __forceinline__ void pb_en_gather(const uint32_t *w, int64_t a, int32_t lo, int32_t hi, uint32_t out[4])
-{
-    const int64_t i = a >> 2; // floor: a is negative only where nothing before byte 0 is wanted
-    const uint32_t sh = (uint32_t)a & 3u;
-    uint32_t d[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t)
-    {
-        const int32_t b = 4 * t - (int32_t)sh; // the dword's first byte among the 16
-        d[t] = (b + 4 > lo && b < hi) ? w[i + t] : 0u;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        out[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
-}
-
-// the last k in [0, PB_EN_WIN) with s_rel[k] <= d
-__device__ __forceinline__ uint32_t pb_en_find(const uint32_t *s_rel, uint32_t d)
-{
-    uint32_t lo = 0, hi = PB_EN_WIN - 1u;
-    while (lo < hi)
-    {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if (s_rel[mid] <= d)
-            lo = mid;
-        else
-            hi = mid - 1u;
-    }
-    return lo;
-}
-
 template <bool VAR>
 __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
 {
@@ -4626,30 +4653,8 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
         return;
     // j0: the record holding the first page's first byte, d0: that byte's offset in the record
     uint64_t j0 = 0, g0 = 0;
-    const uint64_t ob = VAR ? A.offsets[A.first] : 0;
     if (p > 0)
-    {
-        if (VAR)
-        {
-            // P j + offsets[first + j] rises with j: the last j in [0, n] at or below p
-            uint64_t lo = 0, hi = A.n;
-            while (lo < hi)
-            {
-                const uint64_t mid = lo + (hi - lo + 1) / 2;
-                if ((uint64_t)P * mid + (A.offsets[A.first + mid] - ob) <= p)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
-            j0 = lo;
-            g0 = (uint64_t)P * lo + (A.offsets[A.first + lo] - ob);
-        }
-        else
-        {
-            j0 = p / reclen; // the one 64-bit division, once per workgroup
-            g0 = j0 * reclen;
-        }
-    }
+        pb_rp_first<VAR>(A.offsets, A.first, A.n, P, reclen, p, j0, g0);
     int32_t d0 = (int32_t)(p - g0);
     uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
     bool have_win = false;
@@ -4665,21 +4670,16 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             {
                 if (have_win)
                 {
-                    const uint32_t lo = pb_en_find(s_rel, (uint32_t)d0);
+                    const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_EN_WIN - 1u);
                     j0 += lo;
                     d0 -= (int32_t)s_rel[lo];
                 }
                 __syncthreads(); // the window's readers are done
-                offj0 = A.offsets[A.first + (j0 < A.n ? j0 : A.n)];
-                for (uint32_t k = tid; k < PB_EN_WIN; k += PB_EN_WT)
-                {
-                    const uint64_t jj = j0 + k;
-                    s_rel[k] = jj <= A.n ? P * k + (uint32_t)(A.offsets[A.first + jj] - offj0) : 0xFFFFFFFFu;
-                }
+                offj0 = pb_rp_refill(s_rel, PB_EN_WIN, PB_EN_WT, A.offsets, A.first, A.n, P, j0);
                 have_win = true;
             }
             __syncthreads(); // the window is in place, the last page's header readers are done
-            kw = pb_en_find(s_rel, (uint32_t)d0);
+            kw = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_EN_WIN - 1u);
         }
         else
             __syncthreads(); // the last page's header readers are done
@@ -4740,22 +4740,15 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
                     uint32_t x = 0;
 #pragma unroll
                     for (int t = 0; t < 3; ++t)
-                        x ^= __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh) & pb_en_lt(4 * t, vb);
+                        x ^= __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh) & pb_rp_lt(4 * t, vb);
                     x ^= x >> 16;
                     x *= 0x7FEB352Du;
                     x ^= x >> 15;
                     const uint32_t sport = 49152u + (x & 0x3FFFu);
                     T[8] = (T[8] & 0x0000FFFFu) | (pb_bswap16(sport) << 16); // bytes 34-35
                 }
-                // moved to the output's alignment: staged dword u is output bytes hb + 4u .. + 3,
-                // hb the header's first byte rounded down to 4
                 const int32_t hs = (int32_t)rs + S - d0; // the header's first byte in the page (below 0: before it)
-                const uint32_t sh = (uint32_t)hs & 3u;
-                uint32_t *slot = s_hdr + tid * hdw;
-#pragma unroll
-                for (uint32_t u = 0; u < PB_EN_HDW; ++u)
-                    if (u < hdw)
-                        slot[u] = sh ? __builtin_amdgcn_alignbyte(T[u], u ? T[u - 1u] : 0u, 4u - sh) : T[u];
+                pb_rp_stage(s_hdr + tid * hdw, T, hdw, (uint32_t)hs & 3u);
             }
         }
         __syncthreads();
@@ -4770,7 +4763,7 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             uint32_t k, rs, ea;
             if (VAR)
             {
-                k = pb_en_find(s_rel, (uint32_t)d);
+                k = pb_rp_find(s_rel, (uint32_t)d, 0u, PB_EN_WIN - 1u);
                 rs = s_rel[k];
                 ea = s_rel[k + 1u] - rs;
             }
@@ -4790,30 +4783,20 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             const int32_t e3 = bvalid ? (int32_t)ea + S : (int32_t)ea;
             pb_u32x4 v;
             // A wave whose chunks all lie wholly in source bytes behind their record's header (two waves
-            // of three at 1500 B) copies: four aligned dwords and, off alignment, a fifth, which still
-            // holds a byte of the frame.  Decided per wave, so no lane waits for another's path.
+            // of three at 1500 B) copies (a fifth dword still holds a byte of the frame).  Decided per
+            // wave, so no lane waits for another's path.
             if (__ballot(!(r >= sp && r + 16 <= e3)) == 0ull)
-            {
-                const uint64_t a = (uint64_t)(offa + r - (int32_t)P); // at or after the frame's byte S
-                const uint64_t i = a >> 2;
-                const uint32_t sh = (uint32_t)a & 3u;
-                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
-                const uint32_t w4 = sh ? w[i + 4] : 0u;
-                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
-                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
-            }
+                v = pb_rp_copy16(w, (uint64_t)(offa + r - (int32_t)P)); // at or after the frame's byte S
             else
             {
                 uint32_t s0[4] = {0u, 0u, 0u, 0u}, s1[4];
                 {
                     const int32_t lo = (r > sp ? r : sp) - r;
                     const int32_t hi = (r + 16 < e3 ? r + 16 : e3) - r;
-                    pb_en_gather(w, offa + r - (int32_t)P, lo, hi, s1);
+                    pb_rp_gather(w, offa + r - (int32_t)P, lo, hi, s1);
                 }
                 if (S)
-                    pb_en_gather(w, offa + r, 0, S - r, s0);
+                    pb_rp_gather(w, offa + r, 0, S - r, s0);
                 const uint32_t ia = k - kw; // the record's header slot; the next record's is the one after
                 const int32_t hsa = (int32_t)rs + S - d0, hsb = hsa + (int32_t)ea;
                 const int32_t q = 16 * (int32_t)tid;
@@ -4826,7 +4809,7 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
                     const uint32_t vb =
                         bvalid && (uint32_t)(ub + t) < hdw ? s_hdr[(ia + 1u) * hdw + (uint32_t)(ub + t)] : 0u;
                     const int32_t o = r + 4 * t;
-                    const uint32_t m1 = pb_en_lt(o, S), m2 = pb_en_lt(o, sp), m3 = pb_en_lt(o, e3);
+                    const uint32_t m1 = pb_rp_lt(o, S), m2 = pb_rp_lt(o, sp), m3 = pb_rp_lt(o, e3);
                     o4[t] = (s0[t] & m1) | (va & m2 & ~m1) | (s1[t] & m3 & ~m2) | (vb & ~m3);
                 }
                 v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
@@ -4837,12 +4820,7 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
         if (VAR)
             d0 += 4096;
         else
-        {
-            const int32_t dn = d0 + 4096;
-            const uint32_t kn = pb_divq((uint32_t)dn, A.rec);
-            d0 = dn - (int32_t)(kn * reclen);
-            j0 += kn;
-        }
+            pb_rp_next_page(d0, j0, A.rec, reclen);
     }
 }
 
@@ -5048,20 +5026,6 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_map_kernel(pb_fgargs A)
         A.dst_offsets[F + K] = O + L + 34u * (K - 1u);
 }
 
-// the last k in [lo, hi] with s_rel[k] <= d (s_rel[lo] <= d)
-__device__ __forceinline__ uint32_t pb_fg_find(const uint32_t *s_rel, uint32_t d, uint32_t lo, uint32_t hi)
-{
-    while (lo < hi)
-    {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if (s_rel[mid] <= d)
-            lo = mid;
-        else
-            hi = mid - 1u;
-    }
-    return lo;
-}
-
 // Writer, destination-owned as pb_encap_kernel: a workgroup owns `per` consecutive 4-KiB pages of
 // the output, a lane one aligned 16-B chunk of a page per step.  A window of record positions, source
 // positions and map bits is kept in LDS from page to page.  Per page one lane per fragment touching
@@ -5135,7 +5099,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
         // the record holding the page's last byte: the one search of the window per page; a chunk
         // then searches the page's records only (two steps at 1514-B records)
         const uint32_t khi = kw + PB_FG_HREC - 1u < PB_FG_WIN - 1u ? kw + PB_FG_HREC - 1u : PB_FG_WIN - 1u;
-        const uint32_t kend = pb_fg_find(s_rel, (uint32_t)d0 + 4095u, kw, khi);
+        const uint32_t kend = pb_rp_find(s_rel, (uint32_t)d0 + 4095u, kw, khi);
 
         // ---- header stage: the i-th record touching the page, if it is a fragment ----
         for (uint32_t i = tid; kw + i <= kend; i += PB_FG_WT)
@@ -5168,14 +5132,8 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
             T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
             T[5] = (T[5] & 0xFFFF0000u) | pb_bswap16(frag);
             T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
-            // moved to the output's alignment: staged dword u is output bytes hb + 4u .. + 3, hb the
-            // header's first byte rounded down to 4
             const int32_t hs = (int32_t)rs - d0; // the header's first byte in the page (below 0: before it)
-            const uint32_t sh2 = (uint32_t)hs & 3u;
-            uint32_t *slot = s_hdr + i * PB_FG_HDW;
-#pragma unroll
-            for (uint32_t u = 0; u < PB_FG_HDW; ++u)
-                slot[u] = sh2 ? __builtin_amdgcn_alignbyte(T[u], u ? T[u - 1u] : 0u, 4u - sh2) : T[u];
+            pb_rp_stage(s_hdr + i * PB_FG_HDW, T, PB_FG_HDW, (uint32_t)hs & 3u);
         }
         __syncthreads();
 
@@ -5185,7 +5143,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
         if (pc < A.end16)
         {
             // the chunk starts r bytes into record f0 + k (pc is below the output's last byte)
-            const uint32_t k = pb_fg_find(s_rel, (uint32_t)d, kw, kend);
+            const uint32_t k = pb_rp_find(s_rel, (uint32_t)d, kw, kend);
             const uint32_t rs = s_rel[k], meta = s_meta[k];
             const int32_t r = d - (int32_t)rs;
             const bool frag = (meta & PB_FG_M_SPLIT) != 0u;
@@ -5198,22 +5156,13 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
                 slow = slow || (k + c < PB_FG_WIN && (s_meta[k + c] & PB_FG_M_SPLIT) && s_rel[k + c] < (uint32_t)(d + 16));
             pb_u32x4 v;
             if (__ballot(slow) == 0ull)
-            {
-                const uint64_t i = (uint64_t)a >> 2;
-                const uint32_t sh = (uint32_t)a & 3u;
-                const uint32_t w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
-                const uint32_t w4 = sh ? w[i + 4] : 0u; // off alignment it still holds a byte of the chunk
-                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                v.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
-                v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
-            }
+                v = pb_rp_copy16(w, (uint64_t)a);
             else
             {
                 uint32_t o4[4] = {0u, 0u, 0u, 0u};
                 const int32_t lo = (frag && r < 34) ? 34 - r : 0; // the record's data starts here
                 if (lo < hi)
-                    pb_en_gather(w, a, lo, hi, o4);
+                    pb_rp_gather(w, a, lo, hi, o4);
 #pragma unroll
                 for (uint32_t c = 0; c < 3u; ++c)
                 {
@@ -5230,7 +5179,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
                             for (int t = 0; t < 4; ++t)
                             {
                                 const uint32_t val = (uint32_t)(ub + t) < PB_FG_HDW ? slot[(uint32_t)(ub + t)] : 0u;
-                                const uint32_t m = pb_en_lt(4 * t, sb) & ~pb_en_lt(4 * t, sa);
+                                const uint32_t m = pb_rp_lt(4 * t, sb) & ~pb_rp_lt(4 * t, sa);
                                 o4[t] = (o4[t] & ~m) | (val & m);
                             }
                         }
@@ -5238,7 +5187,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
                 }
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    o4[t] &= pb_en_lt(4 * t, hi); // zeros past the output's last byte
+                    o4[t] &= pb_rp_lt(4 * t, hi); // zeros past the output's last byte
                 v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
             }
             *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
@@ -5263,10 +5212,10 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_copy_kernel(pb_fgargs A)
             continue;
         const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
         uint32_t o4[4];
-        pb_en_gather(w, (int64_t)(a0 + pc), 0, hi, o4);
+        pb_rp_gather(w, (int64_t)(a0 + pc), 0, hi, o4);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-            o4[t] &= pb_en_lt(4 * t, hi);
+            o4[t] &= pb_rp_lt(4 * t, hi);
         *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
     }
 }
