@@ -104,7 +104,31 @@ void pbgpu_frames_free(pbgpu_ctx *ctx, pbgpu_frames *frames);
 
 /* ---- hot path: build iterations [first_iter, first_iter + n_iter) ----
  * Asynchronous on the context's stream.  Seeds: pb_config.h seed stream with
- * the seed_base given to pbgpu_load_sequence(). */
+ * the seed_base given to pbgpu_load_sequence().  first_iter + n_iter must stay below
+ * PB_STATIC_SEED_K (2^48 - 1); otherwise -EINVAL, with `out` and the counters unchanged.
+ *
+ * What a build writes (tests/test_gpu_build_bounds.py), with n_frames = n_iter * payloads per
+ * iteration and total = the frames' bytes:
+ *   out->data[0, total)            the frames, packed from byte 0.
+ *   out->data[total, round16(total))  the pad bytes up to the next multiple of 16: zeros, or left as
+ *                                  they were.  The page, line and one-lane-per-frame kernels
+ *                                  (pb_xpage_kernel, pb_ximg_kernel, pb_batch_kernel, pb_small_kernel,
+ *                                  pb_vline_kernel, pb_vpage_kernel) store the last 16-B chunk whole,
+ *                                  zero-filled; the staged and group kernels (pb_fstage_kernel,
+ *                                  pb_stage_kernel, pb_vstage_kernel, pb_gpf_kernel) mask it to the
+ *                                  frame's bytes; pb_xsmall_kernel's streams (64 / 128-B frames) have
+ *                                  no pad.  A caller must not rely on either.
+ *   nothing else in data           not a byte before data, none at or past round16(total): neither the
+ *                                  unused rest of a variable-length build's capacity nor whatever lies
+ *                                  behind the buffer.
+ *   out->offsets                   fixed length: not written.  Variable length: offsets[n_frames] by
+ *                                  the build, offsets[0 .. n_frames) by the build or on first use
+ *                                  (see pbgpu_frames); no entry past offsets[n_frames].
+ *   out->scan_tmp and the buffer's library-internal side arrays are scratch.
+ * So capacity_frames == n_frames and capacity_bytes == round16(n_frames * longest frame) are
+ * sufficient, and a caller may carve one allocation into several buffers (checked with data
+ * pointers that are 4-KiB aligned, as pbgpu_frames_alloc gives them).
+ * pbgpu_build_size's max_bytes has 16 B more than that; pbgpu_frames_alloc adds 64 B for readers. */
 int pbgpu_build(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uint64_t n_iter,
                 pbgpu_frames *out);
 

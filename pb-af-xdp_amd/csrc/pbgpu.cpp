@@ -2013,8 +2013,12 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
                 // buffer's capacity); the page grid covers the longest stream these frames can make
                 if (fe->d_vrec == nullptr)
                     HIPCHK(fb_alloc(ctx, (void **)&fe->d_vrec, out->capacity_frames * sizeof(uint2)));
+                // (every wave of the grid below loads its first page's entry before it looks at the
+                // stream's length, and the grid is whole groups of 32 pages: up to 31 entries past
+                // the buffer's last page are read, never used)
                 if (fe->d_vpt == nullptr)
-                    HIPCHK(hipMalloc((void **)&fe->d_vpt, (out->capacity_bytes / 4096 + 2) * sizeof(uint2)));
+                    HIPCHK(hipMalloc((void **)&fe->d_vpt,
+                                     ((out->capacity_bytes / 4096 + 2 + 31) / 32 * 32) * sizeof(uint2)));
                 K.vp_rec = fe->d_vrec;
                 K.vp_pt = fe->d_vpt;
                 // the grid covers the expected stream (one random payload of uniform length: the
