@@ -201,7 +201,7 @@ typedef struct pbgpu_verify_result {
  * verify_one does (Ethernet + IPv4 without options; the IPv4 header is the 20 bytes at 14, the
  * protocol byte 23; protocols 6 and 17 add the pseudo header; a stored UDP checksum of 0 gets no
  * special case).  A frame shorter than 34 B is bad (SHORT) whatever `checks` says and nothing else
- * is evaluated for it.  codes_out[j] (host memory, n bytes, or NULL) = the OR of the failed bits
+ * is evaluated for it.  Bits above 7 in `checks` are ignored.  codes_out[j] (host memory, n bytes, or NULL) = the OR of the failed bits
  * of frame first_frame + j; first_bad is an index into the buffer.  Ordered on the context's
  * stream after the build or upload of `frames`; returns with the result.  Reads no environment
  * variable and never writes to frames->data.  -EINVAL: a range past n_frames, res == NULL, a

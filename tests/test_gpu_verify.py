@@ -2,7 +2,7 @@
 
 The reference is the oracle's checker, `oracle_binding.verify_frames`, called on one frame at a
 time (n = 1): it says whether a frame is bad.  It stops at the first failing check, so which
-checks failed comes from `ref_code` below, a plain restatement of the same rules (RFC 1071 over
+checks failed comes from `ref_code` (verify_ref.py), a plain restatement of the same rules (RFC 1071 over
 the frame's big-endian words); `ref_codes` asserts for every frame it is given that the two agree
 (oracle says bad <=> ref_code != 0).  Neither is the code under test."""
 import ctypes as C
@@ -16,6 +16,7 @@ import oracle_binding as ob
 import pb_configs as pc
 import pbgpu
 from pbgpu import GpuContext, PbError, Sequence
+from verify_ref import expect, ref_code, ref_codes, ref_one  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,65 +29,6 @@ def ctx():
     c = GpuContext(0)
     yield c
     c.close()
-
-
-# ------------------------------------------------------------------ reference
-def _sum16(b):
-    b = np.asarray(b, dtype=np.uint8)
-    if len(b) & 1:
-        b = np.append(b, np.uint8(0))
-    w = b.reshape(-1, 2).astype(np.uint64)
-    return int(((w[:, 0] << np.uint64(8)) | w[:, 1]).sum())
-
-
-def _fold(s):
-    while s >> 16:
-        s = (s & 0xFFFF) + (s >> 16)
-    return s
-
-
-def ref_code(f):
-    n = len(f)
-    if n < 34:
-        return pbgpu.VERIFY_SHORT
-    code = 0
-    if _fold(_sum16(f[14:34])) != 0xFFFF:
-        code |= pbgpu.VERIFY_IP_CSUM
-    if (int(f[16]) << 8 | int(f[17])) != n - 14:
-        code |= pbgpu.VERIFY_TOT_LEN
-    s, proto = _sum16(f[34:]), int(f[23])
-    if proto in (6, 17):
-        s += _sum16(f[26:34]) + proto + (n - 34)
-    if _fold(s) != 0xFFFF:
-        code |= pbgpu.VERIFY_L4_CSUM
-    return code
-
-
-def ref_one(f):
-    """One frame's code, tied to the oracle's verdict."""
-    f = np.ascontiguousarray(f, dtype=np.uint8)
-    code = ref_code(f)
-    # a one-byte buffer for an empty frame: the checker reads nothing of a short frame
-    oracle_bad = ob.verify_frames(f if len(f) else np.zeros(1, np.uint8), None, len(f), 1, 1)
-    assert oracle_bad == (1 if code else 0), (len(f), code)
-    return code
-
-
-def ref_codes(data, off):
-    return np.array([ref_one(data[int(off[i]):int(off[i + 1])]) for i in range(len(off) - 1)], dtype=np.uint8)
-
-
-def expect(res, codes, ref, first=0):
-    """A VerifyResult and its codes against reference codes of the same range."""
-    assert np.array_equal(codes, ref), np.nonzero(codes != ref)[0][:8]
-    assert res.n_checked == len(ref)
-    assert res.n_bad == int(np.count_nonzero(ref))
-    assert res.bad_short == int(np.count_nonzero(ref & 8))
-    assert res.bad_ip_csum == int(np.count_nonzero(ref & 1))
-    assert res.bad_tot_len == int(np.count_nonzero(ref & 2))
-    assert res.bad_l4_csum == int(np.count_nonzero(ref & 4))
-    bad = np.nonzero(ref)[0]
-    assert res.first_bad == (first + int(bad[0]) if len(bad) else NONE)
 
 
 def uploaded(ctx, data, off=None, flen=0, fb=None):
