@@ -355,6 +355,53 @@ int pbgpu_fragment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame
 int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                    const pbgpu_frag_opts *opts, pbgpu_frames *dst, pbgpu_frag_result *res /* may be NULL */);
 
+/* ---- stamping: a sequence number and a timestamp written into built (or uploaded) frames in place,
+ * the L4 checksum kept valid, on the device ---- */
+#define PBGPU_STAMP_TAIL    1u  /* position counted back from the frame's end; else forward from the L4 payload */
+#define PBGPU_STAMP_NO_CSUM 2u  /* leave the L4 checksum as it is */
+typedef struct pbgpu_stamp_opts {
+    uint64_t t0_ns;        /* time of index 0, ns since the epoch (as pbgpu_pcap_opts)                  */
+    uint64_t step_ps;      /* picoseconds between consecutive frames; 0 = all at t0                     */
+    uint64_t first_index;  /* global index of frame first_frame                                         */
+    uint32_t offset;       /* bytes, <= 65535                                                           */
+    uint32_t flags;        /* PBGPU_STAMP_*; any other bit: -EINVAL                                     */
+} pbgpu_stamp_opts;
+typedef struct pbgpu_stamp_result {
+    uint64_t n_in;         /* frames of the range                                                       */
+    uint64_t n_stamped;
+    uint64_t n_short;      /* eligible, but the 16 bytes do not fit: unchanged                          */
+    uint64_t n_other;      /* not Ethernet + IPv4 without options + unfragmented ICMP/TCP/UDP: unchanged */
+    double   device_ms;    /* the stamp launch, one event pair                                          */
+} pbgpu_stamp_result;
+
+/* For frame first_frame + j of `frames`, bytes F, length L:
+ *   other (unchanged): L < 34, F[12:14] != 08 00, F[14] != 0x45, BE16(F[20:22]) & 0x3FFF != 0 (a
+ *     fragment has no L4 header of its own), F[23] not 1, 6 or 17, or TCP with L >= 47 and
+ *     4 * (F[46] >> 4) < 20.
+ *   H = 8 for ICMP and UDP, 4 * (F[46] >> 4) for TCP (a TCP frame with L < 47 is short); P0 = 34 + H;
+ *   S = P0 + offset, or with TAIL S = L - 16 - offset.
+ *   short (unchanged) unless P0 <= S and S + 16 <= L (the frame length decides, not the stored
+ *     tot_len, as in pbgpu_verify).
+ *   Otherwise F[S : S + 16] = BE64(first_index + j), BE64(T), T = t0_ns + floor((first_index + j) *
+ *     step_ps / 1000): the T that pbgpu_pcap_pack gives record j under the same three values.
+ *   Unless NO_CSUM is set the L4 checksum follows incrementally (RFC 1624 eq. 3): C = BE16 at Q, Q = 40
+ *     for UDP, 50 for TCP, 36 for ICMP; a = S - 34; W = the big-endian 16-bit words of the L4 segment
+ *     at even segment offsets that intersect [a, a + 16) (8 words for even a, 9 for odd a; a byte at or
+ *     past L counts as 0); s = (~C & 0xFFFF) + sum over W of (~old & 0xFFFF) + sum over W of new, folded
+ *     (s = (s & 0xFFFF) + (s >> 16)) until no carry is left; ~s & 0xFFFF is stored at Q.  A stored 0
+ *     gets no special case, as in pbgpu_verify.
+ * No other byte of frames->data changes value: not in the frame, its neighbours, the pad or past it;
+ * n_frames, fixed_len, total_bytes, offsets[], the recorded shortest and longest frame and
+ * pbgpu_counters are unchanged.  Runs on the context's stream after the build or upload of `frames`
+ * and, being a writer, after the landings queued from it; later verifies, landings and repacks see the
+ * stamped bytes.  Returns with the result (res may be NULL).  n == 0 writes nothing.  Reads no
+ * environment variable.
+ * -EINVAL: NULL ctx, frames or opts, a buffer never built or uploaded, a range past n_frames,
+ * unknown flag bits, offset > 65535, (first_index + n - 1) * step_ps >= 2^64 or a last timestamp past
+ * 2^64 ns (as pbgpu_pcap_pack).  On any error nothing is written. */
+int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uint64_t n,
+                const pbgpu_stamp_opts *opts, pbgpu_stamp_result *res /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -408,7 +455,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  *        3 offsetof(pb_sequence_t, ip.ranges), 4 offsetof(pb_sequence_t, pls),
  *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
  *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts),
- *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result);
+ *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result),
+ *        12 sizeof(pbgpu_stamp_opts), 13 sizeof(pbgpu_stamp_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

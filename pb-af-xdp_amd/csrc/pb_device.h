@@ -319,6 +319,25 @@ struct pb_fgargs
     uint64_t *map;           // n_out entries
 };
 
+// ---- stamping (pbgpu_stamp: pb_stamp_kernel) ----
+// In place: frame first + j gets 16 bytes and its L4 checksum field rewritten, by one lane.
+#define PB_SP_WT 256u                // threads per workgroup: one frame each per row
+#define PB_SP_ROWS 4u             // rows of PB_SP_WT frames per workgroup (the result atomics come once per workgroup)
+#define PB_SP_TAIL 1u                // pb_spargs.flags, as PBGPU_STAMP_TAIL / _NO_CSUM
+#define PB_SP_NO_CSUM 2u
+#define PB_SP_RES_DW 4u              // result words: n_stamped, n_short, n_other, 0
+struct pb_spargs
+{
+    uint8_t *data;           // frames->data
+    const uint64_t *offsets; // frames->offsets (variable length), null for fixed length
+    uint64_t first, n;       // frames [first, first + n)
+    uint32_t fixed_len;
+    uint32_t offset;         // the stamp's position, forward from the L4 payload or back from the frame's end
+    uint32_t flags;
+    uint64_t t0_ns, step_ps, first_index;
+    unsigned long long *res; // PB_SP_RES_DW words, zero before the launch
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

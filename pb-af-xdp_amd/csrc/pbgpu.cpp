@@ -51,6 +51,7 @@ extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t 
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -307,6 +308,7 @@ struct pbgpu_ctx
     uint64_t fg_cnt_cap = 0; // source frames
     uint64_t *d_fg_map = nullptr;
     uint64_t fg_map_cap = 0; // output records
+    unsigned long long *d_sp_res = nullptr; // pbgpu_stamp: the result words
     seq_slot seqs[PB_MAX_SEQUENCES];
     std::vector<timing_pair> pending;
     std::vector<timing_pair> pool;
@@ -832,6 +834,8 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipFree(ctx->d_fg_cnt);
     if (ctx->d_fg_map)
         (void)hipFree(ctx->d_fg_map);
+    if (ctx->d_sp_res)
+        (void)hipFree(ctx->d_sp_res);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->d_lens)
@@ -1871,8 +1875,25 @@ static bool buffers_overlap(const pbgpu_frames *src, const pbgpu_frames *dst)
 // Taking a buffer over as the destination of a build, an upload or a repack on `st`: the work
 // follows the buffer's last writer on another stream, and the landings queued from the buffer (a
 // landing never reads frames being overwritten). The lengths are those of the frames to come.
+static int take_inplace(pbgpu_frames *dst, hipStream_t st, frames_events **fe_out);
+
 static int take_dst(pbgpu_frames *dst, hipStream_t st, uint32_t min_len, uint32_t max_len, uint32_t up_max_len1,
                     frames_events **fe_out)
+{
+    frames_events *fe = nullptr;
+    PBCHK(take_inplace(dst, st, &fe));
+    fe->packed32 = false;
+    fe->up_max_len1 = up_max_len1;
+    fe->min_len = min_len;
+    fe->max_len = max_len;
+    if (fe_out)
+        *fe_out = fe;
+    return PBGPU_OK;
+}
+
+// Its sibling for a writer that changes bytes of the frames in place (pbgpu_stamp): the same
+// ordering, while the frames, their offsets and the recorded lengths stay what they are.
+static int take_inplace(pbgpu_frames *dst, hipStream_t st, frames_events **fe_out)
 {
     frames_events *fe = frames_ev(dst);
     if (fe == NULL)
@@ -1885,10 +1906,6 @@ static int take_dst(pbgpu_frames *dst, hipStream_t st, uint32_t min_len, uint32_
         HIPCHK(hipStreamWaitEvent(st, fe->moved, 0));
     }
     fe->last = st;
-    fe->packed32 = false;
-    fe->up_max_len1 = up_max_len1;
-    fe->min_len = min_len;
-    fe->max_len = max_len;
     if (fe->land_pending)
     {
         HIPCHK(hipStreamWaitEvent(st, fe->landed, 0));
@@ -2975,6 +2992,77 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
     return mark_built(ctx, dst, st);
 }
 
+// ---- stamping ----
+
+int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, const pbgpu_stamp_opts *opts,
+                pbgpu_stamp_result *res)
+{
+    if (ctx == NULL || f == NULL || opts == NULL || f->data == NULL)
+        return PBGPU_EINVAL;
+    if ((opts->flags & ~(PBGPU_STAMP_TAIL | PBGPU_STAMP_NO_CSUM)) || opts->offset > 65535u)
+        return PBGPU_EINVAL;
+    if (n)
+    {
+        // as pbgpu_pcap_pack: the device computes the index, its product and the timestamp in 64 bits
+        if (opts->first_index > UINT64_MAX - (n - 1))
+            return PBGPU_EINVAL;
+        const uint64_t last = opts->first_index + (n - 1);
+        if (opts->step_ps && last > UINT64_MAX / opts->step_ps)
+            return PBGPU_EINVAL;
+        if (last * opts->step_ps / 1000u > UINT64_MAX - opts->t0_ns)
+            return PBGPU_EINVAL;
+    }
+    uint64_t body = 0, end = 0;
+    PBCHK(range_bytes(ctx, f, first_frame, n, &body, &end)); // the range check; variable length: offsets[] in place
+    if (end > f->capacity_bytes)
+        return PBGPU_EINVAL;
+    if (res)
+    {
+        memset(res, 0, sizeof *res);
+        res->n_in = n;
+    }
+    if (n == 0)
+        return PBGPU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    hipStream_t st = ctx->stream;
+    if (ctx->d_sp_res == nullptr)
+        HIPCHK(hipMalloc((void **)&ctx->d_sp_res, PB_SP_RES_DW * sizeof(unsigned long long)));
+    PBCHK(take_inplace(f, st, nullptr));
+    pb_spargs A;
+    memset(&A, 0, sizeof A);
+    A.data = f->data;
+    A.offsets = f->fixed_len ? nullptr : f->offsets;
+    A.first = first_frame;
+    A.n = n;
+    A.fixed_len = f->fixed_len;
+    A.offset = opts->offset;
+    A.flags = ((opts->flags & PBGPU_STAMP_TAIL) ? PB_SP_TAIL : 0u) | ((opts->flags & PBGPU_STAMP_NO_CSUM) ? PB_SP_NO_CSUM : 0u);
+    A.t0_ns = opts->t0_ns;
+    A.step_ps = opts->step_ps;
+    A.first_index = opts->first_index;
+    A.res = ctx->d_sp_res;
+    HIPCHK(hipMemsetAsync(ctx->d_sp_res, 0, PB_SP_RES_DW * sizeof(unsigned long long), st));
+    timing_pair tp;
+    PBCHK(timed_begin(ctx, &tp));
+    HIPCHK(pbk_launch_stamp(&A, st));
+    PBCHK(timed_stop(ctx, tp));
+    unsigned long long r[PB_SP_RES_DW] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(r, ctx->d_sp_res, sizeof r, hipMemcpyDeviceToHost, st));
+    float ms = 0;
+    PBCHK(timed_ms(ctx, tp, &ms));
+    if (r[0] + r[1] + r[2] != n)
+        return PBGPU_EIO;
+    if (res)
+    {
+        res->n_stamped = r[0];
+        res->n_short = r[1];
+        res->n_other = r[2];
+        res->device_ms = ms;
+    }
+    return mark_built(ctx, f, st); // a later landing follows the stamp
+}
+
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
 {
     if (ctx == NULL || ptr == NULL)
@@ -3524,6 +3612,8 @@ size_t pbgpu_abi_size(int which)
     case 9: return sizeof(pbgpu_encap_opts);
     case 10: return sizeof(pbgpu_frag_opts);
     case 11: return sizeof(pbgpu_frag_result);
+    case 12: return sizeof(pbgpu_stamp_opts);
+    case 13: return sizeof(pbgpu_stamp_result);
     default: return 0;
     }
 }

@@ -5240,3 +5240,237 @@ extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t gr
         hipLaunchKernelGGL(pb_frag_copy_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, *A);
     return hipGetLastError();
 }
+
+// ---------------- stamping (pbgpu_stamp) ----------------
+// The one post-pass that writes where it reads.  Ownership goes by frame: one lane classifies its
+// frame, reads the 16 bytes at the stamp's position and the stored L4 checksum, and does every
+// store of the frame, so no lane ever reads bytes that another lane writes.  Loads may be wider
+// than the frame's bytes (aligned dwords, the bytes of other frames in them dropped); stores are
+// exact to the byte range, in 1, 2, 4, 8 or 16-B pieces as the address allows.
+
+// The sum of the little-endian 16-bit words of 16 bytes (four dwords in memory order) that start
+// at an even (odd = false) or odd position of the L4 segment; an odd start's neighbour bytes count
+// as 0: they are the same before and after, and cancel exactly in ~old + new.
+__device__ __forceinline__ uint32_t pb_sp_lesum(const uint32_t v[4], bool odd)
+{
+    uint32_t s = 0;
+    if (!odd)
+    {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            s = pb_add_halves(s, v[t]);
+        return s;
+    }
+    s = pb_add_halves(s, v[0] << 8);
+#pragma unroll
+    for (int t = 1; t < 4; ++t)
+        s = pb_add_halves(s, (v[t] << 8) | (v[t - 1] >> 24));
+    return s + (v[3] >> 24);
+}
+
+__device__ __forceinline__ void pb_sp_shr(uint64_t &lo, uint64_t &hi, uint32_t bits)
+{
+    lo = (lo >> bits) | (hi << (64u - bits));
+    hi >>= bits;
+}
+
+// 16 bytes (lo, hi: memory order, little-endian) to p, whatever its alignment: pieces of 1, 2, 4
+// and 8 B up to the next 16-B boundary, then 8, 4, 2 and 1 B behind it; one 16-B store when aligned.
+__device__ __forceinline__ void pb_sp_store16(uint8_t *p, uint64_t lo, uint64_t hi)
+{
+    const uint32_t h = (uint32_t)(0u - (uint32_t)(uintptr_t)p) & 15u;
+    if (h == 0)
+    {
+        *reinterpret_cast<pb_u32x4 *>(p) =
+            pb_u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+        return;
+    }
+    if (h & 1u)
+    {
+        *p = (uint8_t)lo;
+        pb_sp_shr(lo, hi, 8);
+        p += 1;
+    }
+    if (h & 2u)
+    {
+        *reinterpret_cast<uint16_t *>(p) = (uint16_t)lo;
+        pb_sp_shr(lo, hi, 16);
+        p += 2;
+    }
+    if (h & 4u)
+    {
+        *reinterpret_cast<uint32_t *>(p) = (uint32_t)lo;
+        pb_sp_shr(lo, hi, 32);
+        p += 4;
+    }
+    if (h & 8u)
+    {
+        *reinterpret_cast<uint64_t *>(p) = lo;
+        lo = hi;
+        hi = 0;
+        p += 8;
+    }
+    const uint32_t t = 16u - h; // p is 16-B aligned now
+    if (t & 8u)
+    {
+        *reinterpret_cast<uint64_t *>(p) = lo;
+        lo = hi;
+        hi = 0;
+        p += 8;
+    }
+    if (t & 4u)
+    {
+        *reinterpret_cast<uint32_t *>(p) = (uint32_t)lo;
+        pb_sp_shr(lo, hi, 32);
+        p += 4;
+    }
+    if (t & 2u)
+    {
+        *reinterpret_cast<uint16_t *>(p) = (uint16_t)lo;
+        pb_sp_shr(lo, hi, 16);
+        p += 2;
+    }
+    if (t & 1u)
+        *p = (uint8_t)lo;
+}
+
+// One lane per frame, PB_SP_ROWS rows of 256 frames per workgroup; the three result counts are kept
+// in registers across the rows and added once per workgroup.  VAR: addresses from offsets[], else
+// from the fixed length.  A frame shorter than 34 B is never read.
+template <bool VAR>
+__global__ __launch_bounds__(PB_SP_WT) void pb_stamp_kernel(pb_spargs A)
+{
+    __shared__ uint32_t s_red[3 * (PB_SP_WT / 64u)];
+    const uint32_t tid = threadIdx.x, wv = tid >> 6;
+    uint32_t stamped = 0, shrt = 0, other = 0;
+    for (uint32_t ri = 0; ri < PB_SP_ROWS; ++ri)
+    {
+        const uint64_t j = ((uint64_t)blockIdx.x * PB_SP_ROWS + ri) * PB_SP_WT + tid;
+        if (j >= A.n)
+            break;
+        uint64_t o;
+        uint32_t L;
+        if (VAR)
+        {
+            o = A.offsets[A.first + j];
+            L = (uint32_t)(A.offsets[A.first + j + 1] - o);
+        }
+        else
+        {
+            o = (A.first + j) * A.fixed_len;
+            L = A.fixed_len;
+        }
+        if (L < 34u)
+        {
+            other += 1;
+            continue;
+        }
+        uint8_t *F = A.data + o;
+        uint32_t proto;
+        {
+            // bytes 12..23 from aligned dwords inside the frame (bytes 9..27 at the widest)
+            const uintptr_t a = (uintptr_t)(F + 12);
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
+            const uint32_t sh = (uint32_t)a & 3u;
+            const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3];
+            const uint32_t b12 = __builtin_amdgcn_alignbyte(d1, d0, sh); // bytes 12..15
+            const uint32_t b20 = __builtin_amdgcn_alignbyte(d3, d2, sh); // bytes 20..23
+            proto = b20 >> 24;
+            if ((b12 & 0x00FFFFFFu) != 0x00450008u || (pb_bswap16(b20 & 0xFFFFu) & 0x3FFFu) != 0u ||
+                (proto != 1u && proto != 6u && proto != 17u))
+            {
+                other += 1;
+                continue;
+            }
+        }
+        uint32_t H = 8u, Q = proto == 17u ? 40u : 36u;
+        if (proto == 6u)
+        {
+            if (L < 47u)
+            {
+                shrt += 1;
+                continue;
+            }
+            H = 4u * (uint32_t)(F[46] >> 4);
+            Q = 50u;
+            if (H < 20u)
+            {
+                other += 1;
+                continue;
+            }
+        }
+        const int32_t P0 = 34 + (int32_t)H;
+        const int32_t S = (A.flags & PB_SP_TAIL) ? (int32_t)L - 16 - (int32_t)A.offset : P0 + (int32_t)A.offset;
+        if (S < P0 || S + 16 > (int32_t)L)
+        {
+            shrt += 1;
+            continue;
+        }
+        stamped += 1;
+        const uint64_t idx = A.first_index + j;
+        const uint64_t T = A.t0_ns + idx * A.step_ps / 1000ull;
+        uint32_t nw4[4] = {__builtin_bswap32((uint32_t)(idx >> 32)), __builtin_bswap32((uint32_t)idx),
+                           __builtin_bswap32((uint32_t)(T >> 32)), __builtin_bswap32((uint32_t)T)};
+        uint8_t *p = F + S;
+        if (!(A.flags & PB_SP_NO_CSUM))
+        {
+            // the old 16 bytes from aligned dwords; the fifth one only where it starts inside them
+            const uint32_t *w = reinterpret_cast<const uint32_t *>((uintptr_t)p & ~(uintptr_t)3);
+            const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+            uint32_t e[5];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                e[t] = w[t];
+            e[4] = sh ? w[4] : 0u;
+            uint32_t old4[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                old4[t] = __builtin_amdgcn_alignbyte(e[t + 1], e[t], sh);
+            const bool odd = (S & 1) != 0;
+            const uint32_t c = (uint32_t)F[Q] | ((uint32_t)F[Q + 1u] << 8); // little-endian, as the word sums
+            // RFC 1624 eq. 3, byte-swapped throughout (the ones' complement sum commutes with the swap)
+            uint32_t s = (~c & 0xFFFFu) + (odd ? 9u : 8u) * 0xFFFFu - pb_sp_lesum(old4, odd) + pb_sp_lesum(nw4, odd);
+            s = ~pb_fold(s) & 0xFFFFu;
+            if (((uintptr_t)(F + Q) & 1u) == 0)
+                *reinterpret_cast<uint16_t *>(F + Q) = (uint16_t)s;
+            else
+            {
+                F[Q] = (uint8_t)s;
+                F[Q + 1u] = (uint8_t)(s >> 8);
+            }
+        }
+        pb_sp_store16(p, (uint64_t)nw4[0] | ((uint64_t)nw4[1] << 32), (uint64_t)nw4[2] | ((uint64_t)nw4[3] << 32));
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+    {
+        stamped += __shfl_xor(stamped, dd, 64);
+        shrt += __shfl_xor(shrt, dd, 64);
+        other += __shfl_xor(other, dd, 64);
+    }
+    if ((tid & 63u) == 0)
+        s_red[3 * wv + 0] = stamped, s_red[3 * wv + 1] = shrt, s_red[3 * wv + 2] = other;
+    __syncthreads();
+    if (tid == 0)
+    {
+        uint32_t r[3] = {0, 0, 0};
+#pragma unroll
+        for (uint32_t v = 0; v < PB_SP_WT / 64u; ++v)
+            r[0] += s_red[3 * v + 0], r[1] += s_red[3 * v + 1], r[2] += s_red[3 * v + 2];
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+            if (r[t])
+                atomicAdd(A.res + t, (unsigned long long)r[t]);
+    }
+}
+
+extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st)
+{
+    const uint64_t per = (uint64_t)PB_SP_WT * PB_SP_ROWS;
+    const uint32_t grid = (uint32_t)((A->n + per - 1u) / per);
+    if (A->offsets)
+        hipLaunchKernelGGL((pb_stamp_kernel<true>), dim3(grid), dim3(PB_SP_WT), 0, st, *A);
+    else
+        hipLaunchKernelGGL((pb_stamp_kernel<false>), dim3(grid), dim3(PB_SP_WT), 0, st, *A);
+    return hipGetLastError();
+}

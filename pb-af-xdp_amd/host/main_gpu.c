@@ -44,6 +44,9 @@ static int encap_twice;
 /* --fragment MTU[:ignoredf], once: handed to the driver with pb_set_fragment */
 static const char *fragment_spec;
 static int fragment_twice;
+/* --stamp head[:OFF] | tail[:OFF], once: handed to the driver with pb_set_stamp */
+static const char *stamp_spec;
+static int stamp_twice;
 
 static void sign_hdl(int sig)
 {
@@ -56,7 +59,7 @@ enum
     O_INTERFACE = 256, O_BLOCK, O_TRACK, O_MAXPCKTS, O_MAXBYTES, O_PPS, O_BPS, O_DELAY, O_THREADS, O_L4CSUM, O_SMAC,
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
-    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT,
+    O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT, O_STAMP,
 };
 
 static const struct option common_opts[] = {
@@ -97,6 +100,7 @@ static const struct option common_opts[] = {
     {"verify", no_argument, NULL, O_SECOND_PASS},
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
     {"encap", required_argument, NULL, O_ENCAP}, {"fragment", required_argument, NULL, O_FRAGMENT},
+    {"stamp", required_argument, NULL, O_STAMP},
     {NULL, 0, NULL, 0},
 };
 
@@ -190,6 +194,11 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
             if (fragment_spec && fragment_spec != a)
                 fragment_twice = 1;
             fragment_spec = a;
+            break;
+        case O_STAMP:
+            if (stamp_spec && stamp_spec != a)
+                stamp_twice = 1;
+            stamp_spec = a;
             break;
         default: break;
         }
@@ -327,6 +336,36 @@ static int parse_fragment(const char *spec, pbgpu_frag_opts *o, const char **why
     return 0;
 }
 
+/* --stamp's argument head[:OFF] | tail[:OFF] -> the offset and flags; -1 and a message in `why` for a
+ * malformed one */
+static int parse_stamp(const char *spec, pbgpu_stamp_opts *o, const char **why)
+{
+    char buf[32];
+    memset(o, 0, sizeof *o);
+    if (strlen(spec) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    strcpy(buf, spec);
+    char *off = strchr(buf, ':');
+    if (off)
+        *off++ = '\0';
+    if (strcmp(buf, "tail") == 0)
+        o->flags = PBGPU_STAMP_TAIL;
+    else if (strcmp(buf, "head") != 0)
+    {
+        *why = "expected head[:OFF] or tail[:OFF]";
+        return -1;
+    }
+    if (off && field_u32(off, 65535, &o->offset) != 0)
+    {
+        *why = "OFF is 0-65535 bytes";
+        return -1;
+    }
+    return 0;
+}
+
 static void print_cmd_help(void)
 {
     fprintf(stdout, "Usage: pcktbatch-gpu -c <configfile> | -z [overrides] [-v -l -h] [AF_XDP/GPU options]\n\n"
@@ -337,7 +376,8 @@ static void print_cmd_help(void)
                     "-z --cli => Enables the first sequence/packet override (README.md first-sequence options).\n\n"
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
-                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf]\n"
+                    "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf] "
+                    "--stamp head[:OFF]|tail[:OFF]\n"
                     "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
                     "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
                     "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
@@ -347,7 +387,13 @@ static void print_cmd_help(void)
                     "port hashed from the inner frame, DPORT 4789 by default).\n"
                     "--fragment MTU[:ignoredf] => Split every built IPv4 packet longer than MTU (68-65535) into fragments "
                     "on the GPU before it is verified again, encapsulated, sent or dumped; packets with DF set are left "
-                    "whole unless :ignoredf is given. --maxpckts counts built packets, the byte limits what is sent.\n");
+                    "whole unless :ignoredf is given. --maxpckts counts built packets, the byte limits what is sent.\n"
+                    "--stamp head[:OFF] | tail[:OFF] => Write BE64(frame index) and BE64(T ns) into every built ICMP / TCP / "
+                    "UDP frame on the GPU, OFF bytes into its L4 payload (tail: its last 16 bytes, OFF bytes further "
+                    "in), before it is verified, fragmented, encapsulated, sent or dumped; the L4 checksum is updated "
+                    "unless l4csum is 0. T = t0 + index / pps: t0 is --pcapt0 NS (default now), and T is the scheduled "
+                    "time, not the wire time. A frame without room stays as it is. scripts/stamp_read.py reads a "
+                    "capture back.\n");
 }
 
 int main(int argc, char **argv)
@@ -409,6 +455,23 @@ int main(int argc, char **argv)
             return EXIT_FAILURE;
         }
         pb_set_fragment(&fo);
+    }
+    if (stamp_spec)
+    {
+        pbgpu_stamp_opts so;
+        const char *why = NULL;
+        if (stamp_twice)
+        {
+            fprintf(stderr, "--stamp given more than once: one stamp per run.\n");
+            return EXIT_FAILURE;
+        }
+        if (parse_stamp(stamp_spec, &so, &why) != 0)
+        {
+            fprintf(stderr, "--stamp %s: %s.\n", stamp_spec, why);
+            return EXIT_FAILURE;
+        }
+        so.t0_ns = pcapt0_ns; /* --pcapt0 counts without --pcapdump too */
+        pb_set_stamp(&so, pcapt0_set);
     }
     struct cmd_line_af_xdp cmd_af_xdp = {0};
     cmd_line_af_xdp_defaults(&cmd_af_xdp);

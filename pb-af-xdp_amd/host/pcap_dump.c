@@ -2,8 +2,8 @@
  * pcap_dump.c — pcktbatch-gpu --pcapdump (pcap_dump.h).
  *
  * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
- * Batch k is (verified, with --fragment fragmented into a fragment buffer and verified again, with --encap
- * encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
+ * Batch k is (with --stamp stamped in place, verified, with --fragment fragmented into a fragment buffer
+ * and verified again, with --encap encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
  * other frame buffer; then stream k is copied to its host buffer in one piece and written with
  * one write() per buffer (looped only on a short write).
  */
@@ -167,8 +167,26 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         fprintf(stderr, "[%d] Error building frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first, pbgpu_strerror(rc));
         goto out;
     }
+    /* --stamp: the frames that will be packed, with the pack's own t0, step and first index */
+    const pbgpu_stamp_opts *so = pb_get_stamp();
     while (n_cur)
     {
+        if (so)
+        {
+            const uint64_t have0 = src[cur]->n_frames;
+            pbgpu_stamp_opts s = *so;
+            s.t0_ns = t0_ns;
+            s.step_ps = step_ps;
+            s.first_index = packed;
+            if (!seq->l4_csum)
+                s.flags |= PBGPU_STAMP_NO_CSUM;
+            if ((rc = pbgpu_stamp(ctx, src[cur], 0, have0 < quota - done ? have0 : quota - done, &s, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error stamping frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc));
+                goto out;
+            }
+        }
         if (D->cmd->verify)
         {
             pbgpu_verify_result r;

@@ -9,6 +9,9 @@
  * sequence is stamped t0 + floor(j * step / 1000) ns with step = 10^12 / pps ps (0 without pps);
  * the first sequence's t0 is --pcapt0 (else CLOCK_REALTIME at start), the next one's the previous
  * one's t0 + floor(N_prev * step_prev / 1000).  Microsecond format, pb_pcap_open's file header.
+ * With --stamp (pb_set_stamp) a batch's frames are stamped in place before anything else is done
+ * with them, with the t0, step and first index its pack then takes: a record's timestamp is the T
+ * its frame carries.
  */
 #pragma once
 

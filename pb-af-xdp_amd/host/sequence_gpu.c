@@ -62,6 +62,10 @@ static int encap_on; /* --encap (pb_set_encap) */
 static pbgpu_encap_opts encap_opts;
 static int frag_on; /* --fragment (pb_set_fragment) */
 static pbgpu_frag_opts frag_opts;
+static int stamp_on; /* --stamp (pb_set_stamp) */
+static int stamp_t0_set;
+static pbgpu_stamp_opts stamp_opts;
+static uint64_t stamp_t0[PB_MAX_SEQUENCES]; /* t0 of each sequence: --pcapt0, else the clock at its start */
 
 void pb_request_stop(void)
 {
@@ -106,6 +110,19 @@ void pb_set_fragment(const pbgpu_frag_opts *opts)
 const pbgpu_frag_opts *pb_get_fragment(void)
 {
     return frag_on ? &frag_opts : NULL;
+}
+
+void pb_set_stamp(const pbgpu_stamp_opts *opts, int t0_set)
+{
+    stamp_on = opts != NULL;
+    stamp_t0_set = opts != NULL && t0_set;
+    if (opts)
+        stamp_opts = *opts;
+}
+
+const pbgpu_stamp_opts *pb_get_stamp(void)
+{
+    return stamp_on ? &stamp_opts : NULL;
 }
 
 int pb_last_error(void)
@@ -243,6 +260,11 @@ static int gb_fragment(void *h, void *src, const pbgpu_frag_opts *opts, void *ds
     pbgpu_frames *f = (pbgpu_frames *)src;
     return pbgpu_fragment((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
 }
+static int gb_stamp(void *h, void *frames, const pbgpu_stamp_opts *opts)
+{
+    pbgpu_frames *f = (pbgpu_frames *)frames;
+    return pbgpu_stamp((pbgpu_ctx *)h, f, 0, f->n_frames, opts, NULL);
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -254,7 +276,8 @@ static void gb_close(void *h)
 
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
-                                         gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment};
+                                         gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment,
+                                         gb_stamp};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -723,8 +746,25 @@ static void *gpu_worker(void *p)
         last_error = PBGPU_ENOTSUP;
         goto out;
     }
+    /* --stamp: the batch's global frame index and the scheduled time of index 0 */
+    const int stp = stamp_on;
+    pbgpu_stamp_opts sopts = stamp_opts;
+    sopts.t0_ns = stamp_t0[w->seq_idx];
+    sopts.step_ps = seq->pps > 0 ? 1000000000000ull / seq->pps : 0;
+    if (!seq->l4_csum)
+        sopts.flags |= PBGPU_STAMP_NO_CSUM;
     while (!done && !stop_requested && !verify_failed[w->seq_idx])
     {
+        if (stp)
+        {
+            sopts.first_index = (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch * fpi;
+            if ((rc = B->stamp(ctx, fr[cur], &sopts)) != 0)
+            {
+                fprintf(stderr, "[%d] Error stamping frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+        }
         if (w->cmd.verify)
         {
             uint64_t bad = 0, first_bad = 0;
@@ -1106,6 +1146,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
         last_error = PBGPU_ENOTSUP;
         return;
     }
+    if (stamp_on && builder->stamp == NULL)
+    {
+        fprintf(stderr, "[%d] --stamp: this frame builder cannot stamp.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
+    }
     if (cmd.umem_slot && (cmd.umem_slot < 64 || cmd.umem_slot > PB_FRAME_SIZE || (cmd.umem_slot & (cmd.umem_slot - 1)) ||
                           (uint64_t)(cmd.umem_frames ? cmd.umem_frames : PB_NUM_FRAMES) * (PB_FRAME_SIZE / cmd.umem_slot) >
                               (1u << 22)))
@@ -1118,6 +1164,13 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     const uint16_t idx = seq_cnt++;
     start_time[idx] = time(NULL);
     verify_on[idx] = cmd.verify ? 1 : 0;
+    stamp_t0[idx] = stamp_opts.t0_ns;
+    if (stamp_on && !stamp_t0_set)
+    {
+        struct timespec ts;
+        clock_gettime(CLOCK_REALTIME, &ts);
+        stamp_t0[idx] = (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+    }
     shared_umem_t *shared = NULL;
     if (cmd.shared_umem && t_cnt > 0)
     {

@@ -53,6 +53,17 @@ const pbgpu_encap_opts *pb_get_encap(void);
  * default). */
 void pb_set_fragment(const pbgpu_frag_opts *opts);
 const pbgpu_frag_opts *pb_get_fragment(void);
+/* --stamp head[:OFF] | tail[:OFF] (main_gpu.c's own option): every built batch is stamped on the GPU
+ * (pbgpu_stamp) before it is verified, fragmented, encapsulated, landed or packed, so --verify proves
+ * the updated checksums and the fragments of one packet share one stamp.  `opts` carries the offset,
+ * PBGPU_STAMP_TAIL and, with t0_set, t0_ns (--pcapt0); without t0_set t0 is the realtime clock at the
+ * sequence's start.  The driver fills in the rest per batch: step_ps = 10^12 / pps (0 for pps 0),
+ * first_index = the batch's global frame index ((step * n_shards + shard) * batch * frames per
+ * iteration on the TX path, so shards and GPUs never collide; under --pcapdump the pack's own
+ * first_index, t0_ns and step_ps), NO_CSUM exactly when the sequence's l4_csum is 0.  On the TX path T
+ * is the frame's scheduled time, not its wire time.  NULL: none (the default). */
+void pb_set_stamp(const pbgpu_stamp_opts *opts, int t0_set);
+const pbgpu_stamp_opts *pb_get_stamp(void);
 
 void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cmd_line_af_xdp cmd);
 /* sequence.c:779-824: stop and join the workers, print the end-of-run lines,
@@ -115,6 +126,9 @@ typedef struct pb_builder
     int (*alloc_frag)(void *h, uint16_t seq_idx, uint64_t n_iter, const pbgpu_frag_opts *opts, uint32_t extra,
                       void **frames, uint32_t *max_len);
     int (*fragment)(void *h, void *src, const pbgpu_frag_opts *opts, void *dst);
+    /* --stamp: the built batch `frames` stamped in place (pbgpu_stamp over all its frames).  NULL:
+     * --stamp is refused. */
+    int (*stamp)(void *h, void *frames, const pbgpu_stamp_opts *opts);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

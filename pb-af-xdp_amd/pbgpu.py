@@ -246,6 +246,34 @@ class FragResult(C.Structure):
     ]
 
 
+STAMP_TAIL = 1     # position counted back from the frame's end
+STAMP_NO_CSUM = 2  # leave the L4 checksum as it is
+
+
+class StampOpts(C.Structure):
+    """pbgpu_stamp_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("t0_ns", C.c_uint64),
+        ("step_ps", C.c_uint64),
+        ("first_index", C.c_uint64),
+        ("offset", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class StampResult(C.Structure):
+    """pbgpu_stamp_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_in", C.c_uint64),
+        ("n_stamped", C.c_uint64),
+        ("n_short", C.c_uint64),
+        ("n_other", C.c_uint64),
+        ("device_ms", C.c_double),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -407,6 +435,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_fragment_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
         "pbgpu_fragment_bound": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
         "pbgpu_fragment": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), FP, C.POINTER(FragResult)]),
+        "pbgpu_stamp": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(StampOpts), C.POINTER(StampResult)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -564,6 +593,21 @@ class FrameBuffer:
         res = FragResult()
         _check(self.ctx.lib.pbgpu_fragment(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(res)),
                "fragment")
+        return res
+
+    def stamp(self, first: int = 0, n: Optional[int] = None, t0_ns: int = 0, step_ps: int = 0, first_index: int = 0,
+              offset: int = 0, tail: bool = False, csum: bool = True, flags: Optional[int] = None) -> StampResult:
+        """Stamps frames [first, first + n) (n None: to the last frame) in place: BE64(first_index + j)
+        and BE64(t0_ns + (first_index + j) * step_ps / 1000) at `offset` bytes into the L4 payload (tail:
+        back from the frame's end), the L4 checksum updated unless csum is False.  `flags` overrides
+        tail and csum with raw PBGPU_STAMP_* bits.  Returns the StampResult."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        if flags is None:
+            flags = (STAMP_TAIL if tail else 0) | (0 if csum else STAMP_NO_CSUM)
+        opts = StampOpts(t0_ns, step_ps, first_index, offset, flags)
+        res = StampResult()
+        _check(self.ctx.lib.pbgpu_stamp(self.ctx.h, self.ptr, first, n, C.byref(opts), C.byref(res)), "stamp")
         return res
 
     def free(self) -> None:
