@@ -165,7 +165,9 @@ int pbgpu_copy_offsets(pbgpu_ctx *ctx, const pbgpu_frames *frames, uint64_t *hos
  * Runs on the context's landing stream after the build of `frames` only, so a
  * build of another buffer queued meanwhile overlaps it (double buffering);
  * returns when the frames are in place.  A frame longer than slot_stride is
- * refused (-EINVAL). */
+ * refused (-EINVAL) before anything is written: the check uses the buffer's
+ * recorded longest frame (its fixed length, or what its build, upload or repack
+ * noted), so reloading a sequence slot does not change it. */
 int pbgpu_copy_to_umem(pbgpu_ctx *ctx, const pbgpu_frames *frames, void *umem, uint32_t slot_stride,
                        uint32_t first_slot, uint64_t first_frame, uint32_t n, uint16_t *lens_out);
 /* The same, asynchronous: returns once the landing is queued (registered UMEM;

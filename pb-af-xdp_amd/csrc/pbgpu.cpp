@@ -259,11 +259,9 @@ struct frames_events
     uint2 *d_vpt = nullptr;
     bool packed32 = false;
     uint32_t wf = 0;
-    // pbgpu_frames_upload, variable length: the longest uploaded frame + 1 (what a landing checks
-    // against its slot, in place of the building sequence's longest frame); 0 after a build
-    uint32_t up_max_len1 = 0;
     // the buffer's shortest and longest frame: the building sequence's, or the uploaded frames'
-    // (pbgpu_encap refuses frames it cannot encapsulate); both 0 while the buffer holds no frames
+    // (pbgpu_encap refuses frames it cannot encapsulate, a landing frames longer than its slot);
+    // both 0 while the buffer holds no frames
     uint32_t min_len = 0, max_len = 0;
 };
 
@@ -1877,13 +1875,11 @@ static bool buffers_overlap(const pbgpu_frames *src, const pbgpu_frames *dst)
 // landing never reads frames being overwritten). The lengths are those of the frames to come.
 static int take_inplace(pbgpu_frames *dst, hipStream_t st, frames_events **fe_out);
 
-static int take_dst(pbgpu_frames *dst, hipStream_t st, uint32_t min_len, uint32_t max_len, uint32_t up_max_len1,
-                    frames_events **fe_out)
+static int take_dst(pbgpu_frames *dst, hipStream_t st, uint32_t min_len, uint32_t max_len, frames_events **fe_out)
 {
     frames_events *fe = nullptr;
     PBCHK(take_inplace(dst, st, &fe));
     fe->packed32 = false;
-    fe->up_max_len1 = up_max_len1;
     fe->min_len = min_len;
     fe->max_len = max_len;
     if (fe_out)
@@ -1984,7 +1980,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
         st = ctx->seq_stream[si];
     }
     frames_events *fe = nullptr;
-    PBCHK(take_dst(out, st, S.min_flen, S.max_flen, 0, &fe));
+    PBCHK(take_dst(out, st, S.min_flen, S.max_flen, &fe));
     pb_kargs K = S.K;
     K.first_iter = first_iter;
     K.n_frames = nf;
@@ -2552,7 +2548,7 @@ int pbgpu_frames_upload(pbgpu_ctx *ctx, pbgpu_frames *f, const void *host_data, 
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
     hipStream_t st = ctx->stream;
-    PBCHK(take_dst(f, st, (uint32_t)min_len, (uint32_t)max_len, host_offsets ? (uint32_t)max_len + 1 : 0, nullptr));
+    PBCHK(take_dst(f, st, (uint32_t)min_len, (uint32_t)max_len, nullptr));
     if (total)
         HIPCHK(hipMemcpyAsync(f->data, host_data, total, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> off;
@@ -2655,7 +2651,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);
     hipStream_t st = ctx->stream;
-    PBCHK(take_dst(dst, st, 0, 0, 0, nullptr)); // a byte stream: no frames, so no lengths
+    PBCHK(take_dst(dst, st, 0, 0, nullptr)); // a byte stream: no frames, so no lengths
     dst->first_iter = 0;
     dst->n_frames = 0;
     dst->fixed_len = 0;
@@ -2746,8 +2742,7 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
     const frames_events *fs = (const frames_events *)src->reserved;
     const uint32_t src_min = fs->min_len, src_max = fs->max_len;
     hipStream_t st = ctx->stream;
-    PBCHK(take_dst(dst, st, n ? src_min + P : 0, n ? src_max + P : 0, (n && !src->fixed_len) ? src_max + P + 1 : 0,
-                   nullptr));
+    PBCHK(take_dst(dst, st, n ? src_min + P : 0, n ? src_max + P : 0, nullptr));
     float ms = 0;
     if (n)
     {
@@ -2955,8 +2950,7 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
     if (n && !copy)
         PBCHK(scratch_reserve((void **)&ctx->d_fg_map, &ctx->fg_map_cap, n_out, n_out * sizeof(uint64_t)));
     frames_events *fe = nullptr;
-    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, (n && !copy) ? (uint32_t)r[5] + 1u : 0,
-                   &fe));
+    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, &fe));
     float ms = 0;
     if (n)
     {
@@ -3209,9 +3203,7 @@ static int land_unmapped(pbgpu_ctx *ctx, const pbgpu_frames *f, uint8_t *dst, ui
     HIPCHK(hipStreamSynchronize(ls));
     for (uint32_t i = 0; i < n; ++i)
     {
-        const uint64_t len = off[i + 1] - off[i];
-        if (len > slot_stride)
-            return PBGPU_EINVAL;
+        const uint64_t len = off[i + 1] - off[i]; // <= slot_stride: the caller checked the buffer's longest frame
         memcpy(dst + (uint64_t)i * slot_stride, ctx->h_stage + (off[i] - off[0]), len);
         if (lens_out)
             lens_out[i] = (uint16_t)len;
@@ -3233,13 +3225,12 @@ int pbgpu_copy_to_umem_async(pbgpu_ctx *ctx, const pbgpu_frames *f, void *umem, 
     if (n == 0)
         return PBGPU_OK;
     // a frame longer than a slot would overrun the next slot (or, in the last slot,
-    // the UMEM allocation): refused, from the fixed length or the sequence's
-    // longest frame (the reference does not check, af_xdp.c:214)
+    // the UMEM allocation): refused before anything is written, from the fixed length or
+    // the longest frame recorded for the buffer by its build, upload or repack, never from
+    // the sequence slot, which may hold another sequence by now (the reference does not
+    // check, af_xdp.c:214)
     const frames_events *fu = (const frames_events *)f->reserved;
-    if (f->fixed_len     ? f->fixed_len > slot_stride
-        : fu && fu->up_max_len1 ? fu->up_max_len1 - 1 > slot_stride
-                         : (f->seq_idx >= PB_MAX_SEQUENCES || !ctx->seqs[f->seq_idx].loaded ||
-                            ctx->seqs[f->seq_idx].max_flen > slot_stride))
+    if (f->fixed_len ? f->fixed_len > slot_stride : (fu == NULL || fu->max_len > slot_stride))
         return PBGPU_EINVAL;
     HIPCHK(hipSetDevice(ctx->device));
     PB_JOIN(ctx);

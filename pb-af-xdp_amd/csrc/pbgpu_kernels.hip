@@ -3285,9 +3285,14 @@ __global__ __launch_bounds__(256) void pb_scatter_fixed(const uint8_t *src, uint
     const uint32_t *w = reinterpret_cast<const uint32_t *>((uintptr_t)s & ~(uintptr_t)3);
     const uint32_t sh = (uint32_t)((uintptr_t)s & 3);
     // the frame's own dwords read at most 3 bytes past it (inside the buffer's 16-B tail pad);
-    // a filler dword is read only while the stream has the bytes
+    // a filler dword is read as two dwords only while the stream has both, its last bytes one by one
     const bool rd = 4 * i < flen || o + 8 <= src_lim;
-    const uint32_t v = rd ? __builtin_amdgcn_alignbyte(w[1], w[0], sh) : 0u;
+    uint32_t v = 0u;
+    if (rd)
+        v = __builtin_amdgcn_alignbyte(w[1], w[0], sh);
+    else
+        for (uint32_t b = 0; b < 4 && o + b < src_lim; ++b)
+            v |= (uint32_t)s[b] << (8 * b);
     uint8_t *d = dst + f * stride + 4 * i;
     if (4 * i + 4 <= wlen)
         *reinterpret_cast<uint32_t *>(d) = v;
