@@ -404,6 +404,67 @@ typedef struct pbgpu_stamp_result {
 int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uint64_t n,
                 const pbgpu_stamp_opts *opts, pbgpu_stamp_result *res /* may be NULL */);
 
+/* ---- IPv4-to-IPv6 translation: built (or uploaded) frames repacked as IPv6 on the device, stateless
+ * (RFC 7915) with RFC 6052 addresses under a /96 prefix ---- */
+#define PBGPU_XLAT_HASH_FLOW 1u   /* flow label hashed per frame, see below; else opts->flow_label */
+typedef struct pbgpu_xlat_opts {
+    uint8_t  src_prefix[12];   /* the /96 in front of the IPv4 source address, wire order */
+    uint8_t  dst_prefix[12];   /* the same for the destination                            */
+    uint32_t flow_label;       /* < 2^20; else -EINVAL                                    */
+    uint32_t flags;            /* PBGPU_XLAT_*; any other bit: -EINVAL                    */
+    uint64_t reserved;         /* must be 0                                               */
+} pbgpu_xlat_opts;
+typedef struct pbgpu_xlat_result {
+    uint64_t n_in, n_udp, n_tcp, n_icmp;
+    uint64_t n_other;          /* frames of the range that cannot be translated */
+    uint64_t first_other;      /* lowest such index into src, UINT64_MAX if none */
+    double   device_ms;        /* all launches of the call, one event pair */
+} pbgpu_xlat_result;
+
+/* A source frame F of length L (the frame length decides, not the stored tot_len, as in pbgpu_verify)
+ * is translatable when L >= 34, F[12:14] = 08 00, F[14] = 0x45, BE16(F[20:22]) & 0x3FFF = 0 (not a
+ * fragment) and it is UDP (F[23] = 17, L >= 42), TCP (F[23] = 6, L >= 54) or an ICMP echo or echo
+ * reply (F[23] = 1, F[34] = 8 or 0, L >= 42).  Every other frame is `other`.  The output frame has
+ * L + 20 bytes, with tc = F[15] and NH = 17, 6 or 58:
+ *   F[0:12], 86 DD,
+ *   0x60 | tc >> 4, (tc & 15) << 4 | fl >> 16, BE16(fl & 0xFFFF), BE16(L - 34), NH, F[22] (hop limit = TTL),
+ *   src_prefix, F[26:30], dst_prefix, F[30:34],
+ *   F[34:L] with the patches below.
+ * fl = flow_label, or under HASH_FLOW pbgpu_encap's hash x of source bytes 26..37 (up to and including
+ * x ^= x >> 15; for ICMP w2 counts as 0) & 0xFFFFF.
+ * With K = the six big-endian 16-bit words of src_prefix plus the six of dst_prefix, every sum folded
+ * (s = (s & 0xFFFF) + (s >> 16)) until no carry is left:
+ *   UDP:  C = BE16(F[40:42]); s = fold((~C & 0xFFFF) + K); ~s & 0xFFFF goes to output bytes 60..61, a
+ *         result of 0x0000 as 0xFFFF (RFC 8200 8.1).
+ *   TCP:  the same with C = BE16(F[50:52]) to output bytes 70..71; a result of 0x0000 is kept.
+ *   ICMP: output byte 54 = 128 for type 8, 129 for type 0; C = BE16(F[36:38]), w = BE16(F[34:36]), w' = w
+ *         with the new type, PS = the 16 words of the two IPv6 addresses + (L - 34) + 58;
+ *         s = fold((~C & 0xFFFF) + (~w & 0xFFFF) + w' + PS); ~s & 0xFFFF goes to output bytes 56..57, a
+ *         result of 0x0000 kept.
+ * No payload byte is summed.  A stored source checksum of 0 gets no special case, as in pbgpu_verify
+ * and pbgpu_stamp: a UDP frame built without an L4 checksum (l4_csum off) leaves with a wrong one.
+ * This version is strict: if one frame of the range is `other` the call returns -EINVAL and dst stays
+ * byte for byte and field for field as it was; res, if given, still holds the counts, first_other
+ * and device_ms (then the classify pass alone).  Otherwise pbgpu_xlat46 writes the frames packed
+ * from byte 0 of dst->data, zeros up to the next multiple of 16 and nothing past that, and dst is a
+ * frames buffer as after pbgpu_encap: n_frames = n, fixed_len = src->fixed_len + 20 (0 for a
+ * variable-length source), total_bytes, the device offsets[j] = off(first_frame + j) -
+ * off(first_frame) + 20 j for j in [0, n], the shortest and longest frame recorded.  src is only
+ * read; pbgpu_counters is unchanged; no environment variable is read.  Runs on the context's stream
+ * after the build or upload of src and after earlier work on dst and the landings queued from it;
+ * returns when the frames are in place.  n == 0: dst becomes empty, nothing is written.
+ * pbgpu_xlat46_size gives n and the range's bytes + 20 n with no device work beyond reading two
+ * offsets of a variable-length source; it does not look at the frames.
+ * -EINVAL: NULL arguments (res may be NULL), src never built or uploaded, a range past src->n_frames,
+ * src == dst or overlapping data, flow_label >= 2^20, unknown flag bits, reserved != 0, src's longest
+ * frame above 65515, an `other` frame.  -ENOSPC: dst->capacity_frames < n or dst->capacity_bytes below
+ * the output rounded up to 16 (checked before the frames are looked at).  On any error dst is
+ * unchanged. */
+int pbgpu_xlat46_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                      const pbgpu_xlat_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                 const pbgpu_xlat_opts *opts, pbgpu_frames *dst, pbgpu_xlat_result *res /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -458,7 +519,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  *        5 offsetof(pb_sequence_t, pl_cnt), 6 offsetof(pbgpu_frames, total_bytes),
  *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts),
  *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result),
- *        12 sizeof(pbgpu_stamp_opts), 13 sizeof(pbgpu_stamp_result);
+ *        12 sizeof(pbgpu_stamp_opts), 13 sizeof(pbgpu_stamp_result),
+ *        14 sizeof(pbgpu_xlat_opts), 15 sizeof(pbgpu_xlat_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

@@ -338,6 +338,40 @@ struct pb_spargs
     unsigned long long *res; // PB_SP_RES_DW words, zero before the launch
 };
 
+// ---- IPv4-to-IPv6 translation (pbgpu_xlat46: pb_xlat_class_kernel, pb_xlat_kernel) ----
+// Output record j = source frame first + j with its bytes 12..33 (ethertype + IPv4 header, 22 B)
+// replaced by 86 DD + the IPv6 header (42 B): 20 bytes longer, bytes from 54 on are the source's
+// from 34 on.  Only translatable frames reach the writer (UDP and ICMP >= 42 B, TCP >= 54 B), so
+// an output record is at least 62 B and a 16-B chunk holds bytes of at most two records.
+#define PB_XL_WT 256u                // threads per workgroup: one 16-B chunk each (writer), one frame each per row (classify)
+#define PB_XL_ROWS 4u                // classify: rows of PB_XL_WT frames per workgroup (the result atomics come once per workgroup)
+#define PB_XL_ADD 20u                // bytes an output record is longer than its frame
+#define PB_XL_WIN 128u               // variable length: record positions kept in LDS (a page touches at most 68 records of >= 62 B:
+                                     // a first partial one, 66 behind it, a last partial one; and one entry ends the last)
+#define PB_XL_HREC 72u               // header slots per page (>= 68)
+#define PB_XL_TDW 19u                // a staged head: the 54 header bytes and the L4 bytes up to the patched checksum
+                                     // (staged length 58 ICMP, 62 UDP, 72 TCP), moved to its destination's alignment: up to 75 bytes
+#define PB_XL_HDW (PB_XL_TDW + 1u)   // a slot: the staged dwords, then the staged length
+#define PB_XL_HASH 1u                // pb_xlargs.flags, as PBGPU_XLAT_HASH_FLOW
+#define PB_XL_RES_DW 8u              // result words: n_udp, n_tcp, n_icmp, n_other, first_other
+struct pb_xlargs
+{
+    const uint8_t *src;      // src->data (16-B aligned)
+    const uint64_t *offsets; // src->offsets (variable length), null for fixed length
+    uint8_t *dst;            // dst->data (16-B aligned)
+    uint64_t *dst_offsets;   // dst->offsets (variable length)
+    uint64_t first, n;       // frames [first, first + n)
+    uint64_t end16;          // output bytes rounded up to 16: what is written
+    uint32_t fixed_len;
+    pb_div rec;              // fixed length: the record size fixed_len + 20
+    uint32_t flags;
+    uint32_t per;            // pages per workgroup
+    uint32_t flow_label;     // without PB_XL_HASH
+    uint32_t ksum;           // the twelve big-endian 16-bit words of the two prefixes, summed and folded
+    uint32_t tpl[8];         // output bytes 20..51 as little-endian dwords: the prefixes in place, zeros elsewhere
+    unsigned long long *res; // classify: PB_XL_RES_DW words
+};
+
 __device__ __forceinline__ uint32_t pb_mod(uint32_t n, const pb_div &v)
 {
     uint32_t q = (uint32_t)(((uint64_t)n * v.m) >> v.sh);

@@ -52,6 +52,7 @@ extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStre
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st);
+extern "C" hipError_t pbk_launch_xlat(const pb_xlargs *A, int stage, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
                                                uint64_t src_lim, uint8_t *dst, uint32_t stride, hipStream_t st);
 
@@ -307,6 +308,7 @@ struct pbgpu_ctx
     uint64_t *d_fg_map = nullptr;
     uint64_t fg_map_cap = 0; // output records
     unsigned long long *d_sp_res = nullptr; // pbgpu_stamp: the result words
+    unsigned long long *d_xl_res = nullptr; // pbgpu_xlat46: the classify pass's result words
     seq_slot seqs[PB_MAX_SEQUENCES];
     std::vector<timing_pair> pending;
     std::vector<timing_pair> pool;
@@ -834,6 +836,8 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipFree(ctx->d_fg_map);
     if (ctx->d_sp_res)
         (void)hipFree(ctx->d_sp_res);
+    if (ctx->d_xl_res)
+        (void)hipFree(ctx->d_xl_res);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->d_lens)
@@ -3057,6 +3061,137 @@ int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t 
     return mark_built(ctx, f, st); // a later landing follows the stamp
 }
 
+// ---- IPv4-to-IPv6 translation ----
+
+// Argument checks shared by pbgpu_xlat46_size and pbgpu_xlat46, then the frames' bytes (range_bytes).
+static int xlat_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_xlat_opts *opts,
+                      uint64_t *body, uint64_t *src_end)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || src->reserved == NULL)
+        return PBGPU_EINVAL;
+    if (opts->flow_label >= (1u << 20) || (opts->flags & ~PBGPU_XLAT_HASH_FLOW) || opts->reserved != 0)
+        return PBGPU_EINVAL;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (src->n_frames && fs->max_len > 65535u - PB_XL_ADD)
+        return PBGPU_EINVAL;
+    return range_bytes(ctx, src, first, n, body, src_end);
+}
+
+int pbgpu_xlat46_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                      const pbgpu_xlat_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    uint64_t body = 0, src_end = 0;
+    PBCHK(xlat_check(ctx, src, first_frame, n, opts, &body, &src_end));
+    *frames = n;
+    *bytes = body + n * PB_XL_ADD;
+    return PBGPU_OK;
+}
+
+int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_xlat_opts *opts,
+                 pbgpu_frames *dst, pbgpu_xlat_result *res)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
+        return PBGPU_EINVAL;
+    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+        return PBGPU_EINVAL;
+    uint64_t body = 0, src_end = 0;
+    PBCHK(xlat_check(ctx, src, first_frame, n, opts, &body, &src_end));
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    const uint64_t total = body + n * PB_XL_ADD;
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (n > dst->capacity_frames || end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    if (n > (uint64_t)0xFFFFFFFFu * (PB_XL_WT * PB_XL_ROWS))
+        return PBGPU_EINVAL;
+    if (res)
+    {
+        memset(res, 0, sizeof *res);
+        res->n_in = n;
+        res->first_other = UINT64_MAX;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const uint32_t src_min = fs->min_len, src_max = fs->max_len;
+    hipStream_t st = ctx->stream;
+    pb_xlargs A;
+    memset(&A, 0, sizeof A);
+    timing_pair tp = {nullptr, nullptr};
+    float ms = 0;
+    if (n)
+    {
+        if (ctx->d_xl_res == nullptr)
+            HIPCHK(hipMalloc((void **)&ctx->d_xl_res, PB_XL_RES_DW * sizeof(unsigned long long)));
+        A.src = src->data;
+        A.offsets = src->fixed_len ? nullptr : src->offsets;
+        A.first = first_frame;
+        A.n = n;
+        A.end16 = end16;
+        A.fixed_len = src->fixed_len;
+        A.rec = make_div(src->fixed_len + PB_XL_ADD);
+        A.flags = (opts->flags & PBGPU_XLAT_HASH_FLOW) ? PB_XL_HASH : 0u;
+        A.flow_label = opts->flow_label;
+        A.res = ctx->d_xl_res;
+        uint8_t t[32]; // output bytes 20..51
+        memset(t, 0, sizeof t);
+        memcpy(t + 2, opts->src_prefix, 12);
+        memcpy(t + 18, opts->dst_prefix, 12);
+        for (int i = 0; i < 32; i += 2)
+            A.ksum += ((uint32_t)t[i] << 8) | t[i + 1];
+        while (A.ksum >> 16)
+            A.ksum = (A.ksum & 0xFFFFu) + (A.ksum >> 16);
+        for (uint32_t i = 0; i < 8; ++i)
+            A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
+                       ((uint32_t)t[4 * i + 3] << 24);
+        // the timed stretch: classify and writer; the classify result is read before anything of dst is touched
+        PBCHK(timed_begin(ctx, &tp));
+        HIPCHK(pbk_launch_xlat(&A, 0, 0, st));
+        unsigned long long r[PB_XL_RES_DW];
+        HIPCHK(hipMemcpyAsync(r, ctx->d_xl_res, sizeof r, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (r[0] + r[1] + r[2] + r[3] != n)
+            return PBGPU_EIO;
+        if (res)
+        {
+            res->n_udp = r[0];
+            res->n_tcp = r[1];
+            res->n_icmp = r[2];
+            res->n_other = r[3];
+            res->first_other = r[4];
+        }
+        if (r[3])
+        {
+            PBCHK(timed_stop(ctx, tp));
+            PBCHK(timed_ms(ctx, tp, &ms));
+            if (res)
+                res->device_ms = ms;
+            return PBGPU_EINVAL;
+        }
+    }
+    // every frame of the range is translatable: at least 42 B
+    PBCHK(take_dst(dst, st, n ? src_min + PB_XL_ADD : 0, n ? src_max + PB_XL_ADD : 0, nullptr));
+    if (n)
+    {
+        A.dst = dst->data;
+        A.dst_offsets = dst->offsets;
+        uint32_t grid = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
+        HIPCHK(pbk_launch_xlat(&A, 1, grid, st)); // variable length: dst->offsets by a launch of its own first
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &ms));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = n;
+    dst->fixed_len = src->fixed_len ? src->fixed_len + PB_XL_ADD : 0;
+    dst->total_bytes = total;
+    if (res)
+        res->device_ms = ms;
+    return mark_built(ctx, dst, st);
+}
+
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)
 {
     if (ctx == NULL || ptr == NULL)
@@ -3605,6 +3740,8 @@ size_t pbgpu_abi_size(int which)
     case 11: return sizeof(pbgpu_frag_result);
     case 12: return sizeof(pbgpu_stamp_opts);
     case 13: return sizeof(pbgpu_stamp_result);
+    case 14: return sizeof(pbgpu_xlat_opts);
+    case 15: return sizeof(pbgpu_xlat_result);
     default: return 0;
     }
 }

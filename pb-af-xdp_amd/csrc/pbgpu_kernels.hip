@@ -5479,3 +5479,365 @@ extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st)
         hipLaunchKernelGGL((pb_stamp_kernel<false>), dim3(grid), dim3(PB_SP_WT), 0, st, *A);
     return hipGetLastError();
 }
+
+// ---------------- IPv4-to-IPv6 translation (pbgpu_xlat46) ----------------
+// RFC 7915 with RFC 6052 /96 prefixes.  Output record j is source frame first + j with bytes 12..33
+// (ethertype and IPv4 header) replaced by 86 DD and the 40-B IPv6 header: 20 bytes longer, every
+// byte from output byte 54 on at its source position + 20 (j + 1), of which the ICMP type and the
+// L4 checksum are patched.  Two stages: classify (which frames translate; the host reads the
+// result and refuses the call before anything of dst is touched) and the destination-owned writer.
+
+__global__ __launch_bounds__(64) void pb_xlat_init_kernel(unsigned long long *res)
+{
+    if (threadIdx.x < PB_XL_RES_DW)
+        res[threadIdx.x] = threadIdx.x == 4u ? ~0ull : 0ull;
+}
+
+// Classify: one lane per frame, PB_XL_ROWS rows of 256 frames per workgroup, the four counts and the
+// lowest untranslatable index kept in registers across the rows: the result atomics come once per
+// workgroup.  A frame shorter than 34 B is never read; of the others bytes 12..23 come from aligned
+// dwords inside the frame, and byte 34 of an ICMP frame of at least 42 B.
+template <bool VAR>
+__global__ __launch_bounds__(PB_XL_WT) void pb_xlat_class_kernel(pb_xlargs A)
+{
+    __shared__ uint32_t s_red[4 * (PB_XL_WT / 64u)];
+    __shared__ unsigned long long s_min[PB_XL_WT / 64u];
+    const uint32_t tid = threadIdx.x, wv = tid >> 6;
+    uint32_t cnt[4] = {0, 0, 0, 0}; // UDP, TCP, ICMP, other
+    unsigned long long fo = ~0ull;
+    for (uint32_t ri = 0; ri < PB_XL_ROWS; ++ri)
+    {
+        const uint64_t j = ((uint64_t)blockIdx.x * PB_XL_ROWS + ri) * PB_XL_WT + tid;
+        if (j >= A.n)
+            break;
+        uint64_t o;
+        uint32_t L;
+        if (VAR)
+        {
+            o = A.offsets[A.first + j];
+            L = (uint32_t)(A.offsets[A.first + j + 1] - o);
+        }
+        else
+        {
+            o = (A.first + j) * A.fixed_len;
+            L = A.fixed_len;
+        }
+        uint32_t cls = 3u;
+        if (L >= 34u)
+        {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+            const uint64_t a = o + 12u, i = a >> 2;
+            const uint32_t sh = (uint32_t)a & 3u;
+            const uint32_t d0 = w[i], d1 = w[i + 1], d2 = w[i + 2], d3 = w[i + 3]; // bytes 9..27 at the widest
+            const uint32_t b12 = __builtin_amdgcn_alignbyte(d1, d0, sh); // bytes 12..15
+            const uint32_t b20 = __builtin_amdgcn_alignbyte(d3, d2, sh); // bytes 20..23
+            const uint32_t proto = b20 >> 24;
+            if ((b12 & 0x00FFFFFFu) == 0x00450008u && (pb_bswap16(b20 & 0xFFFFu) & 0x3FFFu) == 0u)
+            {
+                if (proto == 17u && L >= 42u)
+                    cls = 0u;
+                else if (proto == 6u && L >= 54u)
+                    cls = 1u;
+                else if (proto == 1u && L >= 42u)
+                {
+                    const uint32_t type = A.src[o + 34u];
+                    if (type == 8u || type == 0u)
+                        cls = 2u;
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; ++c)
+            cnt[c] += cls == c ? 1u : 0u;
+        if (cls == 3u && A.first + j < fo)
+            fo = A.first + j;
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+    {
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; ++c)
+            cnt[c] += __shfl_xor(cnt[c], dd, 64);
+        const uint32_t lo = __shfl_xor((uint32_t)fo, dd, 64), hi = __shfl_xor((uint32_t)(fo >> 32), dd, 64);
+        const unsigned long long m = ((unsigned long long)hi << 32) | lo;
+        fo = m < fo ? m : fo;
+    }
+    if ((tid & 63u) == 0)
+    {
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; ++c)
+            s_red[4 * wv + c] = cnt[c];
+        s_min[wv] = fo;
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        uint32_t r[4] = {0, 0, 0, 0};
+        unsigned long long m = ~0ull;
+#pragma unroll
+        for (uint32_t v = 0; v < PB_XL_WT / 64u; ++v)
+        {
+#pragma unroll
+            for (uint32_t c = 0; c < 4u; ++c)
+                r[c] += s_red[4 * v + c];
+            m = s_min[v] < m ? s_min[v] : m;
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; ++c)
+            if (r[c])
+                atomicAdd(A.res + c, (unsigned long long)r[c]);
+        if (r[3])
+            atomicMin(A.res + 4, m);
+    }
+}
+
+// Writer, destination-owned as pb_encap_kernel: a workgroup owns `per` consecutive 4-KiB pages of the
+// output, a lane one aligned 16-B chunk of a page per step, so every byte has one writer and every
+// store is an aligned 16-B store.  Here bytes are replaced, not only inserted (22 B by 42 B), and
+// the patched L4 bytes lie behind them, so per page one lane per
+// record touching the page stages the record's whole head in LDS: the 54 header bytes and the L4
+// bytes behind them up to the patched checksum (staged length 58 for ICMP, 62 for UDP, 72 for TCP:
+// never more than the record), at the alignment they have in the output, with the staged length in
+// the slot's last dword.  After a barrier a chunk's bytes below its record's staged length come
+// from the slot, those above it from the source 20 bytes back, and what follows the record's end
+// from the next record's slot (a record is at least 62 B: a chunk holds bytes of at most two) or,
+// past the range, zeros.  A wave whose chunks all lie behind their record's staged head takes a
+// plain shifted copy; the choice is per wave, never per lane.
+template <bool VAR>
+__global__ __launch_bounds__(PB_XL_WT) void pb_xlat_kernel(pb_xlargs A)
+{
+    // variable length: output positions of PB_XL_WIN records from record j0 on, relative to it
+    // (below 128 * 65535); 0xFFFFFFFF past the end of the range
+    __shared__ uint32_t s_rel[PB_XL_WIN];
+    // slot i: the head of the i-th record touching the page
+    __shared__ uint32_t s_hdr[PB_XL_HREC * PB_XL_HDW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
+    const uint32_t reclen = A.fixed_len + PB_XL_ADD;
+    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
+    if (p >= A.end16)
+        return;
+    // j0: the record holding the first page's first byte, d0: that byte's offset in the record
+    uint64_t j0 = 0, g0 = 0;
+    if (p > 0)
+        pb_rp_first<VAR>(A.offsets, A.first, A.n, PB_XL_ADD, reclen, p, j0, g0);
+    int32_t d0 = (int32_t)(p - g0);
+    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
+    bool have_win = false;
+    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    {
+        // variable length: the window is kept from page to page and moved to the record holding the
+        // page's first byte only when it no longer reaches the record after the page's last byte
+        uint32_t kw = 0; // the window's index of the record holding the page's first byte
+        if (VAR)
+        {
+            if (!have_win || (int64_t)s_rel[PB_XL_WIN - 1u] <= (int64_t)d0 + 4095)
+            {
+                if (have_win)
+                {
+                    const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_XL_WIN - 1u);
+                    j0 += lo;
+                    d0 -= (int32_t)s_rel[lo];
+                }
+                __syncthreads(); // the window's readers are done
+                offj0 = pb_rp_refill(s_rel, PB_XL_WIN, PB_XL_WT, A.offsets, A.first, A.n, PB_XL_ADD, j0);
+                have_win = true;
+            }
+            __syncthreads(); // the window is in place, the last page's slot readers are done
+            kw = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_XL_WIN - 1u);
+        }
+        else
+            __syncthreads(); // the last page's slot readers are done
+        const uint64_t fj0 = VAR ? 0 : (A.first + j0) * A.fixed_len; // fixed length: frame first + j0's offset in src
+
+        // ---- head stage: lane i stages the head of the i-th record touching the page ----
+        if (tid < PB_XL_HREC)
+        {
+            const uint32_t k = kw + tid;
+            bool act;
+            uint32_t rs = 0, rlen = reclen; // the record's start relative to record j0, its length
+            if (VAR)
+            {
+                act = k + 1u < PB_XL_WIN;
+                if (act)
+                {
+                    rs = s_rel[k];
+                    const uint32_t re = s_rel[k + 1u];
+                    act = re != 0xFFFFFFFFu; // entries j0 + k and j0 + k + 1 are at most n
+                    rlen = re - rs;
+                }
+            }
+            else
+            {
+                rs = k * reclen;
+                act = j0 + k < A.n;
+            }
+            if (act && (int64_t)rs < (int64_t)d0 + 4096)
+            {
+                const uint32_t L = rlen - PB_XL_ADD;
+                // source bytes 0..51 as G[u] = bytes 4u .. 4u + 3, from aligned dwords that start inside the frame
+                const uint64_t so = VAR ? offj0 + (rs - PB_XL_ADD * k) : fj0 + (uint64_t)k * A.fixed_len;
+                const uint64_t i = so >> 2, end = so + L;
+                const uint32_t sh = (uint32_t)so & 3u;
+                uint32_t d[14], G[13];
+#pragma unroll
+                for (int t = 0; t < 14; ++t)
+                    d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
+#pragma unroll
+                for (int t = 0; t < 13; ++t)
+                    G[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
+                const uint32_t tc = G[3] >> 24, proto = G[5] >> 24;
+                uint32_t fl = A.flow_label;
+                if (A.flags & PB_XL_HASH)
+                {
+                    // pbgpu_encap's hash of source bytes 26..37; an ICMP frame has no ports: w2 = 0
+                    uint32_t x = __builtin_amdgcn_alignbyte(G[7], G[6], 2) ^ __builtin_amdgcn_alignbyte(G[8], G[7], 2);
+                    if (proto != 1u)
+                        x ^= __builtin_amdgcn_alignbyte(G[9], G[8], 2);
+                    x ^= x >> 16;
+                    x *= 0x7FEB352Du;
+                    x ^= x >> 15;
+                    fl = x & 0xFFFFFu;
+                }
+                uint32_t T[PB_XL_TDW];
+                T[0] = G[0], T[1] = G[1], T[2] = G[2];
+                T[3] = 0xDD86u | ((0x60u | (tc >> 4)) << 16) | ((((tc & 15u) << 4) | (fl >> 16)) << 24);
+                T[4] = pb_bswap16(fl & 0xFFFFu) | (pb_bswap16(L - 34u) << 16);
+                const uint32_t nh = proto == 1u ? 58u : proto;
+                T[5] = A.tpl[0] | nh | (G[5] & 0x00FF0000u) >> 8; // next header, hop limit = the TTL
+                T[6] = A.tpl[1], T[7] = A.tpl[2];
+                T[8] = A.tpl[3] | (G[6] & 0xFFFF0000u);  // source bytes 26, 27
+                T[9] = A.tpl[4] | (G[7] & 0x0000FFFFu);  // 28, 29
+                T[10] = A.tpl[5], T[11] = A.tpl[6];
+                T[12] = A.tpl[7] | (G[7] & 0xFFFF0000u); // 30, 31
+#pragma unroll
+                for (int t = 0; t < 5; ++t)
+                    T[13 + t] = G[8 + t]; // output bytes 52..71 = source bytes 32..51
+                T[18] = 0u;
+                uint32_t sl;
+                if (proto == 17u)
+                {
+                    const uint32_t c = pb_bswap16(G[10] & 0xFFFFu); // source bytes 40, 41
+                    uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
+                    r = r ? r : 0xFFFFu;
+                    T[15] = (G[10] & 0xFFFF0000u) | pb_bswap16(r);
+                    sl = 62u;
+                }
+                else if (proto == 6u)
+                {
+                    const uint32_t c = pb_bswap16(G[12] >> 16); // source bytes 50, 51
+                    const uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
+                    T[17] = (G[12] & 0x0000FFFFu) | (pb_bswap16(r) << 16);
+                    sl = 72u;
+                }
+                else
+                {
+                    const uint32_t wo = pb_bswap16(G[8] >> 16); // type, code
+                    const uint32_t nt = (wo >> 8) == 8u ? 128u : 129u;
+                    const uint32_t wn = (nt << 8) | (wo & 0xFFu);
+                    const uint32_t c = pb_bswap16(G[9] & 0xFFFFu); // source bytes 36, 37
+                    const uint32_t ps = A.ksum + pb_bswap16(G[6] >> 16) + pb_bswap16(G[7] & 0xFFFFu) +
+                                        pb_bswap16(G[7] >> 16) + pb_bswap16(G[8] & 0xFFFFu) + (L - 34u) + 58u;
+                    const uint32_t r = ~pb_fold((~c & 0xFFFFu) + (~wo & 0xFFFFu) + wn + ps) & 0xFFFFu;
+                    T[13] = (G[8] & 0xFF00FFFFu) | (nt << 16);
+                    T[14] = (G[9] & 0xFFFF0000u) | pb_bswap16(r);
+                    sl = 58u;
+                }
+                const int32_t hs = (int32_t)rs - d0; // the record's first byte in the page (below 0: before it)
+                uint32_t *slot = s_hdr + tid * PB_XL_HDW;
+                pb_rp_stage(slot, T, PB_XL_TDW, (uint32_t)hs & 3u);
+                slot[PB_XL_TDW] = sl;
+            }
+        }
+        __syncthreads();
+
+        // ---- chunks ----
+        const int32_t d = d0 + 16 * (int32_t)tid;
+        const uint64_t pc = p + 16u * tid;
+        if (pc < A.end16)
+        {
+            // k, r: the chunk starts r bytes into record j0 + k, which is ea bytes long; pc is
+            // below the output's last byte, so that record is inside the range
+            uint32_t k, rs, ea;
+            if (VAR)
+            {
+                k = pb_rp_find(s_rel, (uint32_t)d, 0u, PB_XL_WIN - 1u);
+                rs = s_rel[k];
+                ea = s_rel[k + 1u] - rs;
+            }
+            else
+            {
+                k = pb_divq((uint32_t)d, A.rec);
+                rs = k * reclen;
+                ea = reclen;
+            }
+            const int32_t r = d - (int32_t)rs;
+            const bool bvalid = j0 + k + 1u < A.n; // a next record: its first bytes may end the chunk
+            // the record's byte b >= its staged length is source byte offa + b
+            const int64_t offa =
+                (int64_t)(VAR ? offj0 + (rs - PB_XL_ADD * k) : fj0 + (uint64_t)k * A.fixed_len) - (int64_t)PB_XL_ADD;
+            const uint32_t ia = k - kw; // the record's slot; the next record's is the one after
+            const int32_t sl = (int32_t)s_hdr[ia * PB_XL_HDW + PB_XL_TDW];
+            const int32_t e3 = (int32_t)ea;
+            pb_u32x4 v;
+            if (__ballot(!(r >= sl && r + 16 <= e3)) == 0ull)
+                v = pb_rp_copy16(w, (uint64_t)(offa + r));
+            else
+            {
+                uint32_t s1[4];
+                {
+                    const int32_t lo = (r > sl ? r : sl) - r;
+                    const int32_t hi = (r + 16 < e3 ? r + 16 : e3) - r;
+                    pb_rp_gather(w, offa + r, lo, hi, s1);
+                }
+                const int32_t hsa = (int32_t)rs - d0, hsb = hsa + (int32_t)ea;
+                const int32_t q = 16 * (int32_t)tid;
+                const int32_t ua = (q - (hsa & ~3)) >> 2, ub = (q - (hsb & ~3)) >> 2;
+                uint32_t o4[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                {
+                    const uint32_t va = (uint32_t)(ua + t) < PB_XL_TDW ? s_hdr[ia * PB_XL_HDW + (uint32_t)(ua + t)] : 0u;
+                    const uint32_t vb = bvalid && (uint32_t)(ub + t) < PB_XL_TDW
+                                            ? s_hdr[(ia + 1u) * PB_XL_HDW + (uint32_t)(ub + t)]
+                                            : 0u;
+                    const int32_t o = r + 4 * t;
+                    const uint32_t m1 = pb_rp_lt(o, sl), m3 = pb_rp_lt(o, e3);
+                    o4[t] = (va & m1) | (s1[t] & m3 & ~m1) | (vb & ~m3);
+                }
+                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+            }
+            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
+        }
+        // the next page's first byte: 4096 on in the same window, or a whole number of records on
+        if (VAR)
+            d0 += 4096;
+        else
+            pb_rp_next_page(d0, j0, A.rec, reclen);
+    }
+}
+
+// stage 0: the result words and the classify pass; stage 1: dst->offsets (variable length, by
+// pb_encap_offsets_kernel) and the writer
+extern "C" hipError_t pbk_launch_xlat(const pb_xlargs *A, int stage, uint32_t grid, hipStream_t st)
+{
+    if (stage == 0)
+    {
+        const uint64_t per = (uint64_t)PB_XL_WT * PB_XL_ROWS;
+        const uint32_t cg = (uint32_t)((A->n + per - 1u) / per);
+        hipLaunchKernelGGL(pb_xlat_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        if (A->offsets)
+            hipLaunchKernelGGL((pb_xlat_class_kernel<true>), dim3(cg), dim3(PB_XL_WT), 0, st, *A);
+        else
+            hipLaunchKernelGGL((pb_xlat_class_kernel<false>), dim3(cg), dim3(PB_XL_WT), 0, st, *A);
+    }
+    else if (A->offsets)
+    {
+        hipLaunchKernelGGL(pb_encap_offsets_kernel, dim3((uint32_t)((A->n + 256u) / 256u)), dim3(256), 0, st,
+                           A->offsets, A->first, A->n, PB_XL_ADD, A->dst_offsets);
+        hipLaunchKernelGGL((pb_xlat_kernel<true>), dim3(grid), dim3(PB_XL_WT), 0, st, *A);
+    }
+    else
+        hipLaunchKernelGGL((pb_xlat_kernel<false>), dim3(grid), dim3(PB_XL_WT), 0, st, *A);
+    return hipGetLastError();
+}

@@ -47,6 +47,9 @@ static int fragment_twice;
 /* --stamp head[:OFF] | tail[:OFF], once: handed to the driver with pb_set_stamp */
 static const char *stamp_spec;
 static int stamp_twice;
+/* --xlat6 SRC6/96[,DST6/96][:hashflow], once: handed to the driver with pb_set_xlat */
+static const char *xlat_spec;
+static int xlat_twice;
 
 static void sign_hdl(int sig)
 {
@@ -60,6 +63,7 @@ enum
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
     O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT, O_STAMP,
+    O_XLAT6,
 };
 
 static const struct option common_opts[] = {
@@ -100,7 +104,7 @@ static const struct option common_opts[] = {
     {"verify", no_argument, NULL, O_SECOND_PASS},
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
     {"encap", required_argument, NULL, O_ENCAP}, {"fragment", required_argument, NULL, O_FRAGMENT},
-    {"stamp", required_argument, NULL, O_STAMP},
+    {"stamp", required_argument, NULL, O_STAMP}, {"xlat6", required_argument, NULL, O_XLAT6},
     {NULL, 0, NULL, 0},
 };
 
@@ -199,6 +203,11 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
             if (stamp_spec && stamp_spec != a)
                 stamp_twice = 1;
             stamp_spec = a;
+            break;
+        case O_XLAT6:
+            if (xlat_spec && xlat_spec != a)
+                xlat_twice = 1;
+            xlat_spec = a;
             break;
         default: break;
         }
@@ -366,6 +375,76 @@ static int parse_stamp(const char *spec, pbgpu_stamp_opts *o, const char **why)
     return 0;
 }
 
+/* one SRC6/96 of --xlat6 -> its 12 prefix bytes */
+static int parse_prefix96(const char *s, uint8_t out[12], const char **why)
+{
+    char buf[64];
+    uint8_t a[16];
+    const char *slash = strchr(s, '/');
+    if (slash == NULL || strcmp(slash, "/96") != 0)
+    {
+        *why = "a prefix is written ADDR6/96: only /96 prefixes (RFC 6052) are translated";
+        return -1;
+    }
+    if ((size_t)(slash - s) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    memcpy(buf, s, (size_t)(slash - s));
+    buf[slash - s] = '\0';
+    if (inet_pton(AF_INET6, buf, a) != 1)
+    {
+        *why = "not an IPv6 address";
+        return -1;
+    }
+    if (a[12] | a[13] | a[14] | a[15])
+    {
+        *why = "address bits set beyond the /96 prefix";
+        return -1;
+    }
+    memcpy(out, a, 12);
+    return 0;
+}
+
+/* --xlat6's argument SRC6/96[,DST6/96][:hashflow] -> the options; -1 and a message in `why` for a
+ * malformed one.  The suffix follows "/96", so its colon is none of an address's. */
+static int parse_xlat(const char *spec, pbgpu_xlat_opts *o, const char **why)
+{
+    char buf[160];
+    memset(o, 0, sizeof *o);
+    if (strlen(spec) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    strcpy(buf, spec);
+    char *sfx = strstr(buf, "/96:");
+    if (sfx)
+    {
+        char *last;
+        while ((last = strstr(sfx + 1, "/96:")) != NULL) /* the suffix follows the last prefix */
+            sfx = last;
+        sfx[3] = '\0';
+        if (strcmp(sfx + 4, "hashflow") != 0)
+        {
+            *why = "expected SRC6/96[,DST6/96][:hashflow]";
+            return -1;
+        }
+        o->flags = PBGPU_XLAT_HASH_FLOW;
+    }
+    char *second = strchr(buf, ',');
+    if (second)
+        *second++ = '\0';
+    if (parse_prefix96(buf, o->src_prefix, why) != 0)
+        return -1;
+    if (second == NULL)
+        memcpy(o->dst_prefix, o->src_prefix, 12);
+    else if (parse_prefix96(second, o->dst_prefix, why) != 0)
+        return -1;
+    return 0;
+}
+
 static void print_cmd_help(void)
 {
     fprintf(stdout, "Usage: pcktbatch-gpu -c <configfile> | -z [overrides] [-v -l -h] [AF_XDP/GPU options]\n\n"
@@ -377,7 +456,7 @@ static void print_cmd_help(void)
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
                     "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf] "
-                    "--stamp head[:OFF]|tail[:OFF]\n"
+                    "--stamp head[:OFF]|tail[:OFF] --xlat6 SRC6/96[,DST6/96][:hashflow]\n"
                     "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
                     "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
                     "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
@@ -393,7 +472,12 @@ static void print_cmd_help(void)
                     "in), before it is verified, fragmented, encapsulated, sent or dumped; the L4 checksum is updated "
                     "unless l4csum is 0. T = t0 + index / pps: t0 is --pcapt0 NS (default now), and T is the scheduled "
                     "time, not the wire time. A frame without room stays as it is. scripts/stamp_read.py reads a "
-                    "capture back.\n");
+                    "capture back.\n"
+                    "--xlat6 SRC6/96[,DST6/96][:hashflow] => Translate every built frame to IPv6 on the GPU (RFC 7915, "
+                    "stateless) after it is stamped and verified and before it is encapsulated, sent or dumped: the IPv4 "
+                    "addresses go behind the /96 prefixes (RFC 6052; one prefix serves both), TOS and TTL carry over, the "
+                    "TCP / UDP / ICMP echo checksums are updated. :hashflow hashes the flow label from addresses and "
+                    "ports (default 0). Not with --fragment, nor with a UDP sequence whose l4csum is 0.\n");
 }
 
 int main(int argc, char **argv)
@@ -473,6 +557,27 @@ int main(int argc, char **argv)
         so.t0_ns = pcapt0_ns; /* --pcapt0 counts without --pcapdump too */
         pb_set_stamp(&so, pcapt0_set);
     }
+    if (xlat_spec)
+    {
+        pbgpu_xlat_opts xo;
+        const char *why = NULL;
+        if (xlat_twice)
+        {
+            fprintf(stderr, "--xlat6 given more than once: one translation per run.\n");
+            return EXIT_FAILURE;
+        }
+        if (parse_xlat(xlat_spec, &xo, &why) != 0)
+        {
+            fprintf(stderr, "--xlat6 %s: %s.\n", xlat_spec, why);
+            return EXIT_FAILURE;
+        }
+        if (fragment_spec)
+        {
+            fprintf(stderr, "--xlat6 does not combine with --fragment: IPv6 frames are not fragmented here.\n");
+            return EXIT_FAILURE;
+        }
+        pb_set_xlat(&xo);
+    }
     struct cmd_line_af_xdp cmd_af_xdp = {0};
     cmd_line_af_xdp_defaults(&cmd_af_xdp);
     optind = 0; /* main.c:45 */
@@ -518,6 +623,17 @@ int main(int argc, char **argv)
                 (unsigned long long)cmd_af_xdp.seed_base, cmd_af_xdp.literal_payload, cmd_af_xdp.single_fold,
                 cmd_af_xdp.pcap ? cmd_af_xdp.pcap : "(none)", cmd_af_xdp.tx ? cmd_af_xdp.tx : "ring",
                 cmd_af_xdp.umem_frames, cmd_af_xdp.umem_slot ? cmd_af_xdp.umem_slot : 4096u);
+        if (pb_get_xlat())
+        {
+            const pbgpu_xlat_opts *xo = pb_get_xlat();
+            uint8_t a[16] = {0};
+            char s6[INET6_ADDRSTRLEN], d6[INET6_ADDRSTRLEN];
+            memcpy(a, xo->src_prefix, 12);
+            inet_ntop(AF_INET6, a, s6, sizeof s6);
+            memcpy(a, xo->dst_prefix, 12);
+            inet_ntop(AF_INET6, a, d6, sizeof d6);
+            fprintf(stdout, "XLAT6: src=%s/96 dst=%s/96 hashflow=%u\n", s6, d6, xo->flags & PBGPU_XLAT_HASH_FLOW);
+        }
         for (int i = 0; i < seq_cnt; ++i)
             fprintf(stdout, "Sequence #%d: %s -> %s proto %s, %u payload(s)\n", i + 1,
                     cfg->seq[i].ip.src_ip ? cfg->seq[i].ip.src_ip

@@ -3,7 +3,8 @@
  *
  * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
  * Batch k is (with --stamp stamped in place, verified, with --fragment fragmented into a fragment buffer
- * and verified again, with --encap encapsulated into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
+ * and verified again, with --xlat6 translated to IPv6 into a buffer of its own, with --encap encapsulated
+ * into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
  * other frame buffer; then stream k is copied to its host buffer in one piece and written with
  * one write() per buffer (looped only on a short write).
  */
@@ -50,6 +51,8 @@ int pb_pcap_dump_check(const pb_config_t *cfg, int seq_cnt, const struct cmd_lin
             fprintf(stderr, "[%d] --pcapdump needs a packet count (--maxpckts / \"maxpckts\") above 0.\n", i + 1);
             return PBGPU_EINVAL;
         }
+        if (pb_xlat_refuses(s, i + 1) != 0)
+            return PBGPU_EINVAL;
     }
     return PBGPU_OK;
 }
@@ -89,6 +92,7 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
     pbgpu_frames *src[2] = {NULL, NULL}, *dst[2] = {NULL, NULL};
     pbgpu_frames *enc = NULL; /* --encap: the batch as it is packed (the pack returns before the next encap) */
     pbgpu_frames *frg = NULL; /* --fragment: the batch's fragments (what is encapsulated, or packed) */
+    pbgpu_frames *x6 = NULL;  /* --xlat6: the batch as IPv6 (what is encapsulated, or packed) */
     uint8_t *hb[2] = {NULL, NULL};
     int reg[2] = {0, 0};
     int rc;
@@ -110,7 +114,10 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         eopts = *pb_get_encap();
     memcpy(eopts.dst_mac, dmac, 6);
     memcpy(eopts.src_mac, smac, 6);
-    const uint32_t extra = encap ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u;
+    /* --xlat6: 20 more bytes a frame, ahead of the encapsulation's (never beside --fragment) */
+    const pbgpu_xlat_opts *xo = pb_get_xlat();
+    const uint32_t xextra = xo ? 20u : 0u;
+    const uint32_t extra = (encap ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u) + xextra;
     const uint32_t fpi = seq->pl_cnt < 1 ? 1u : seq->pl_cnt;
     const uint64_t quota = seq->max_pckts;
     uint64_t batch = D->cmd->gpu_batch ? D->cmd->gpu_batch : (1u << 20);
@@ -143,6 +150,8 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
     }
     const uint64_t cap = 24 + (16 + extra) * of + obytes + 16;
     if (encap && (rc = pbgpu_frames_alloc(ctx, of, obytes + extra * of + 16, &enc)) != 0)
+        goto out;
+    if (xo && (rc = pbgpu_frames_alloc(ctx, of, obytes + xextra * of + 16, &x6)) != 0)
         goto out;
     const size_t page = (size_t)sysconf(_SC_PAGESIZE);
     for (int i = 0; i < 2; ++i)
@@ -237,6 +246,16 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
                 }
             }
         }
+        if (xo)
+        {
+            if ((rc = pbgpu_xlat46(ctx, bf, 0, btake, xo, x6, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error translating frames to IPv6 on GPU %d :: %s%s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc), rc == PBGPU_EINVAL ? " (a frame that is not UDP, TCP or an ICMP echo?)" : "");
+                goto out;
+            }
+            bf = x6;
+        }
         if (encap && (rc = pbgpu_encap(ctx, bf, 0, btake, &eopts, enc, NULL)) != 0)
         {
             fprintf(stderr, "[%d] Error encapsulating frames on GPU %d :: %s%s.\n", seq_num, D->cmd->gpu_first,
@@ -302,6 +321,7 @@ out:
     }
     pbgpu_frames_free(ctx, enc);
     pbgpu_frames_free(ctx, frg);
+    pbgpu_frames_free(ctx, x6);
     *n_done = done;
     *n_packed = packed;
     *b_packed = packed_b;
@@ -381,6 +401,10 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
     if (pb_get_encap() && !pb_get_fragment())
         for (int i = 0; i < ran; ++i)
             b[i] += written[i] * (pb_get_encap()->mode == PBGPU_ENCAP_VLAN ? 4u : 50u);
+    /* --xlat6: and the 20 bytes the IPv6 header is longer by */
+    if (pb_get_xlat())
+        for (int i = 0; i < ran; ++i)
+            b[i] += written[i] * 20u;
     for (int i = 0; i < ran; ++i)
     {
         /* --fragment: the packets are the built ones (the quota's), the bytes what the file holds, and

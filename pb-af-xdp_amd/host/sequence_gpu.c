@@ -18,11 +18,13 @@
 #include "mac.h"
 #include "xsk_ring.h"
 
+#include <arpa/inet.h>
 #include <errno.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -66,6 +68,8 @@ static int stamp_on; /* --stamp (pb_set_stamp) */
 static int stamp_t0_set;
 static pbgpu_stamp_opts stamp_opts;
 static uint64_t stamp_t0[PB_MAX_SEQUENCES]; /* t0 of each sequence: --pcapt0, else the clock at its start */
+static int xlat_on; /* --xlat6 (pb_set_xlat) */
+static pbgpu_xlat_opts xlat_opts;
 
 void pb_request_stop(void)
 {
@@ -123,6 +127,38 @@ void pb_set_stamp(const pbgpu_stamp_opts *opts, int t0_set)
 const pbgpu_stamp_opts *pb_get_stamp(void)
 {
     return stamp_on ? &stamp_opts : NULL;
+}
+
+void pb_set_xlat(const pbgpu_xlat_opts *opts)
+{
+    xlat_on = opts != NULL;
+    if (opts)
+        xlat_opts = *opts;
+}
+
+const pbgpu_xlat_opts *pb_get_xlat(void)
+{
+    return xlat_on ? &xlat_opts : NULL;
+}
+
+int pb_xlat_refuses(const pb_sequence_t *seq, int seq_num)
+{
+    if (!xlat_on)
+        return 0;
+    if (frag_on)
+    {
+        fprintf(stderr, "[%d] --xlat6 does not combine with --fragment: IPv6 frames are not fragmented here.\n", seq_num);
+        return PBGPU_EINVAL;
+    }
+    if ((seq->ip.protocol == NULL || strcasecmp(seq->ip.protocol, "udp") == 0) && !seq->l4_csum)
+    {
+        fprintf(stderr,
+                "[%d] --xlat6: a UDP sequence needs its L4 checksum (l4csum 1): IPv6 has no UDP checksum of zero, and "
+                "the translation updates the checksum it finds.\n",
+                seq_num);
+        return PBGPU_EINVAL;
+    }
+    return 0;
 }
 
 int pb_last_error(void)
@@ -265,6 +301,11 @@ static int gb_stamp(void *h, void *frames, const pbgpu_stamp_opts *opts)
     pbgpu_frames *f = (pbgpu_frames *)frames;
     return pbgpu_stamp((pbgpu_ctx *)h, f, 0, f->n_frames, opts, NULL);
 }
+static int gb_xlat(void *h, void *src, const pbgpu_xlat_opts *opts, void *dst)
+{
+    pbgpu_frames *f = (pbgpu_frames *)src;
+    return pbgpu_xlat46((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -277,7 +318,7 @@ static void gb_close(void *h)
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
                                          gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment,
-                                         gb_stamp};
+                                         gb_stamp, gb_alloc_encap, gb_xlat}; /* a translation's buffer is sized as an encapsulation's */
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -402,10 +443,11 @@ static void tx_sink(void *ctx, const uint8_t *frame, uint32_t len, uint64_t addr
  * The source is the configured src_ip string, else the frame's drawn source address (rand_ip's
  * dotted string); the ports are the UDP / TCP header's (0 for ICMP), the destination the
  * configured dst_ip string.  Under --encap vlan the one 802.1Q tag (ethertype 0x8100 at byte 12) is
- * skipped; under --encap vxlan the line reports the outer addresses and ports: what is sent. */
+ * skipped; under --encap vxlan the line reports the outer addresses and ports: what is sent.  An
+ * IPv6 frame (--xlat6) reports its own addresses and ports. */
 static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, const uint8_t *fr, uint16_t len)
 {
-    char sip[16], dip[16];
+    char sip[INET6_ADDRSTRLEN], dip[INET6_ADDRSTRLEN];
     const char *src = seq->ip.src_ip;
     const char *dst = seq->ip.dst_ip;
     uint32_t sport = 0, dport = 0;
@@ -418,7 +460,17 @@ static void print_sent(int seq_num, uint32_t pl_idx, const pb_sequence_t *seq, c
     }
     if (len >= 18 && fr[12] == 0x81 && fr[13] == 0x00) /* one 802.1Q tag (--encap vlan): the addresses behind it */
         fr += 4, len -= 4;
-    if (len >= 34)
+    if (len >= 58 && fr[12] == 0x86 && fr[13] == 0xDD)
+    {
+        src = inet_ntop(AF_INET6, fr + 22, sip, sizeof sip);
+        dst = inet_ntop(AF_INET6, fr + 38, dip, sizeof dip);
+        if (fr[20] == 17 || fr[20] == 6)
+        {
+            sport = ((uint32_t)fr[54] << 8) | fr[55];
+            dport = ((uint32_t)fr[56] << 8) | fr[57];
+        }
+    }
+    else if (len >= 34)
     {
         if (src == NULL)
         {
@@ -510,6 +562,7 @@ static void *gpu_worker(void *p)
     void *fr[2] = {NULL, NULL};
     void *efr[2] = {NULL, NULL}; /* --encap: what is landed */
     void *ffr[2] = {NULL, NULL}; /* --fragment: the batch's fragments (what is encapsulated, or landed) */
+    void *xfr[2] = {NULL, NULL}; /* --xlat6: the batch as IPv6 (what is encapsulated, or landed) */
     uint8_t *umem = NULL;
     int registered = 0;
     pb_xsk_t xsk;
@@ -555,6 +608,11 @@ static void *gpu_worker(void *p)
     /* --encap: the outer MACs are the sequence's */
     const int enc = encap_on;
     pbgpu_encap_opts eopts = encap_opts;
+    /* --xlat6: every frame grows by 20 bytes before it is encapsulated (never beside --fragment) */
+    const int xl = xlat_on;
+    const pbgpu_xlat_opts xopts = xlat_opts;
+    const uint32_t xl_extra = xl ? 20u : 0u;
+    max_flen += xl_extra;
     const uint32_t enc_extra = enc ? (eopts.mode == PBGPU_ENCAP_VLAN ? 4u : 50u) : 0u;
     memcpy(eopts.dst_mac, dmac, 6);
     memcpy(eopts.src_mac, smac, 6);
@@ -619,19 +677,39 @@ static void *gpu_worker(void *p)
             goto out;
         }
     }
+    if (xl)
+    {
+        uint32_t longest = 0;
+        if ((rc = B->alloc_xlat(ctx, w->seq_idx, batch, xl_extra, &xfr[0], &longest)) != 0 ||
+            (rc = B->alloc_xlat(ctx, w->seq_idx, batch, xl_extra, &xfr[1], &longest)) != 0)
+        {
+            last_error = rc;
+            goto out;
+        }
+        const uint32_t slot = w->cmd.umem_slot ? w->cmd.umem_slot : PB_FRAME_SIZE;
+        if (longest + xl_extra + enc_extra > slot || longest + xl_extra + enc_extra > 65535u)
+        {
+            fprintf(stderr,
+                    "[%d] --xlat6: the sequence's longest frame (%u B) plus 20 B%s does not fit a %u-B UMEM slot.\n",
+                    seq_num, longest, enc ? " and the encapsulation's" : "", slot < 65535u ? slot : 65535u);
+            last_error = PBGPU_EINVAL;
+            goto out;
+        }
+    }
     if (enc)
     {
         uint32_t longest = 0;
         /* from the fragment buffer: sized for the fragments, and the longest frame is a fragment's */
         if (frg ? (rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, enc_extra, &efr[0], &longest)) != 0 ||
                       (rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, enc_extra, &efr[1], &longest)) != 0
-                : (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[0], &longest)) != 0 ||
-                      (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra, &efr[1], &longest)) != 0)
+                : (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra + xl_extra, &efr[0], &longest)) != 0 ||
+                      (rc = B->alloc_encap(ctx, w->seq_idx, batch, enc_extra + xl_extra, &efr[1], &longest)) != 0)
         {
             last_error = rc;
             goto out;
         }
         const uint32_t slot = w->cmd.umem_slot ? w->cmd.umem_slot : PB_FRAME_SIZE;
+        longest += xl_extra;
         if (longest + enc_extra > slot || longest + enc_extra > 65535u)
         {
             fprintf(stderr, "[%d] --encap: the sequence's longest frame (%u B) plus %u B does not fit a %u-B UMEM slot.\n",
@@ -815,7 +893,14 @@ static void *gpu_worker(void *p)
                 }
             }
         }
-        void *const bf = frg ? ffr[cur] : fr[cur]; /* the batch as it is encapsulated or landed */
+        if (xl && (rc = B->xlat(ctx, fr[cur], &xopts, xfr[cur])) != 0)
+        {
+            fprintf(stderr, "[%d] Error translating frames to IPv6 on GPU %d :: %s%s.\n", seq_num, w->gpu, pbgpu_strerror(rc),
+                    rc == PBGPU_EINVAL ? " (a frame that is not UDP, TCP or an ICMP echo?)" : "");
+            last_error = rc;
+            break;
+        }
+        void *const bf = xl ? xfr[cur] : frg ? ffr[cur] : fr[cur]; /* the batch as it is encapsulated or landed */
         if (enc)
         {
             if ((rc = B->encap(ctx, bf, &eopts, efr[cur])) != 0)
@@ -1093,6 +1178,8 @@ out:
             B->free_frames(ctx, efr[i]);
         if (ffr[i])
             B->free_frames(ctx, ffr[i]);
+        if (xfr[i])
+            B->free_frames(ctx, xfr[i]);
     }
     if (ctx)
         B->close(ctx);
@@ -1121,6 +1208,11 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     if (t_cnt > PB_MAX_WORKERS - worker_cnt)
         t_cnt = PB_MAX_WORKERS - worker_cnt;
     /* refusals come before the sequence takes a slot (its counters and totals line) */
+    if (pb_xlat_refuses(&seq, seq_cnt + 1) != 0)
+    {
+        last_error = PBGPU_EINVAL;
+        return;
+    }
     if (builder->device_count)
     {
         int n_dev = 0;
@@ -1149,6 +1241,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     if (stamp_on && builder->stamp == NULL)
     {
         fprintf(stderr, "[%d] --stamp: this frame builder cannot stamp.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
+    }
+    if (xlat_on && (builder->xlat == NULL || builder->alloc_xlat == NULL))
+    {
+        fprintf(stderr, "[%d] --xlat6: this frame builder cannot translate to IPv6.\n", seq_cnt + 1);
         last_error = PBGPU_ENOTSUP;
         return;
     }

@@ -64,6 +64,15 @@ const pbgpu_frag_opts *pb_get_fragment(void);
  * is the frame's scheduled time, not its wire time.  NULL: none (the default). */
 void pb_set_stamp(const pbgpu_stamp_opts *opts, int t0_set);
 const pbgpu_stamp_opts *pb_get_stamp(void);
+/* --xlat6 SRC6/96[,DST6/96][:hashflow] (main_gpu.c's own option): every built batch is translated to
+ * IPv6 on the GPU (pbgpu_xlat46) after it is stamped and verified and before it is encapsulated,
+ * landed or packed.  NULL: none (the default). */
+void pb_set_xlat(const pbgpu_xlat_opts *opts);
+const pbgpu_xlat_opts *pb_get_xlat(void);
+/* What --xlat6 refuses of a sequence, with the reason on stderr: --fragment beside it (an IPv6
+ * frame is not one the fragmenter splits), a UDP sequence without an L4 checksum (its zero
+ * checksum would leave wrong: IPv6 has no "none").  0: the sequence can be translated. */
+int pb_xlat_refuses(const pb_sequence_t *seq, int seq_num);
 
 void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cmd_line_af_xdp cmd);
 /* sequence.c:779-824: stop and join the workers, print the end-of-run lines,
@@ -129,6 +138,12 @@ typedef struct pb_builder
     /* --stamp: the built batch `frames` stamped in place (pbgpu_stamp over all its frames).  NULL:
      * --stamp is refused. */
     int (*stamp)(void *h, void *frames, const pbgpu_stamp_opts *opts);
+    /* --xlat6: a buffer for n_iter iterations' frames with `extra` more bytes each (20, and the
+     * encapsulation's when one follows), and the sequence's longest frame; the built batch `src`
+     * translated into such a buffer (pbgpu_xlat46), which then encapsulates and lands like a built
+     * one.  NULL: --xlat6 is refused. */
+    int (*alloc_xlat)(void *h, uint16_t seq_idx, uint64_t n_iter, uint32_t extra, void **frames, uint32_t *max_len);
+    int (*xlat)(void *h, void *src, const pbgpu_xlat_opts *opts, void *dst);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

@@ -274,6 +274,50 @@ class StampResult(C.Structure):
     ]
 
 
+XLAT_HASH_FLOW = 1  # the flow label hashed per frame from the addresses and ports
+
+
+class XlatOpts(C.Structure):
+    """pbgpu_xlat_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("src_prefix", C.c_uint8 * 12),
+        ("dst_prefix", C.c_uint8 * 12),
+        ("flow_label", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+    @classmethod
+    def make(cls, src_prefix: bytes, dst_prefix: Optional[bytes] = None, flow_label: int = 0,
+             hash_flow: bool = False) -> "XlatOpts":
+        """The two /96 prefixes as 12 bytes in wire order (dst_prefix None: the source's)."""
+        o = cls()
+        if dst_prefix is None:
+            dst_prefix = src_prefix
+        if len(src_prefix) != 12 or len(dst_prefix) != 12:
+            raise ValueError("a /96 prefix is 12 bytes")
+        o.src_prefix = (C.c_uint8 * 12).from_buffer_copy(bytes(src_prefix))
+        o.dst_prefix = (C.c_uint8 * 12).from_buffer_copy(bytes(dst_prefix))
+        o.flow_label = flow_label
+        o.flags = XLAT_HASH_FLOW if hash_flow else 0
+        return o
+
+
+class XlatResult(C.Structure):
+    """pbgpu_xlat_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_in", C.c_uint64),
+        ("n_udp", C.c_uint64),
+        ("n_tcp", C.c_uint64),
+        ("n_icmp", C.c_uint64),
+        ("n_other", C.c_uint64),
+        ("first_other", C.c_uint64),
+        ("device_ms", C.c_double),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -436,6 +480,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_fragment_bound": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
         "pbgpu_fragment": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), FP, C.POINTER(FragResult)]),
         "pbgpu_stamp": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(StampOpts), C.POINTER(StampResult)]),
+        "pbgpu_xlat46_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), U64P, U64P]),
+        "pbgpu_xlat46": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), FP, C.POINTER(XlatResult)]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -610,6 +656,22 @@ class FrameBuffer:
         _check(self.ctx.lib.pbgpu_stamp(self.ctx.h, self.ptr, first, n, C.byref(opts), C.byref(res)), "stamp")
         return res
 
+    def xlat46(self, dst: "FrameBuffer", first: int = 0, n: Optional[int] = None, opts: Optional[XlatOpts] = None,
+               res: Optional[XlatResult] = None) -> XlatResult:
+        """Translates frames [first, first + n) (n None: to the last frame) to IPv6 into dst (RFC 7915
+        under the /96 prefixes of opts, an XlatOpts), which is then a frames buffer like a built one.
+        One frame that cannot be translated refuses the whole call (PbError -22), dst untouched; a
+        caller's own `res` then still holds the counts.  Returns the XlatResult."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        if opts is None:
+            raise TypeError("xlat46 needs an XlatOpts")
+        if res is None:
+            res = XlatResult()
+        _check(self.ctx.lib.pbgpu_xlat46(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(res)),
+               "xlat46")
+        return res
+
     def free(self) -> None:
         if self.ptr is not None:
             self.ctx.lib.pbgpu_frames_free(self.ctx.h, self.ptr)
@@ -733,6 +795,15 @@ class GpuContext:
         nbytes = C.c_uint64()
         _check(self.lib.pbgpu_pcap_size(self.h, fb.ptr, first, n, flags, C.byref(nbytes)), "pcap_size")
         return int(nbytes.value)
+
+    def xlat46_size(self, fb: "FrameBuffer", first: int, n: Optional[int], opts: XlatOpts):
+        """(frames, bytes) of the IPv6 translation of fb's frames [first, first + n) (n None: to the last frame)."""
+        if n is None:
+            n = int(fb.f.n_frames) - first
+        frames, nbytes = C.c_uint64(), C.c_uint64()
+        _check(self.lib.pbgpu_xlat46_size(self.h, fb.ptr, first, n, C.byref(opts), C.byref(frames), C.byref(nbytes)),
+               "xlat46_size")
+        return int(frames.value), int(nbytes.value)
 
     def encap_size(self, fb: "FrameBuffer", first: int, n: Optional[int], opts: EncapOpts):
         """(frames, bytes) of the encapsulation of fb's frames [first, first + n) (n None: to the last frame)."""
