@@ -465,6 +465,73 @@ int pbgpu_xlat46_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, u
 int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                  const pbgpu_xlat_opts *opts, pbgpu_frames *dst, pbgpu_xlat_result *res /* may be NULL */);
 
+/* ---- verification as sent: frames of any shape this library produces, parsed from their own bytes
+ * on the device ---- */
+#define PBGPU_WIRE_L3_CSUM   1u   /* every IPv4 header parsed folds to 0xFFFF (all 4*IHL bytes)        */
+#define PBGPU_WIRE_L3_LEN    2u   /* IPv4 tot_len / IPv6 payload length agree with the frame's length  */
+#define PBGPU_WIRE_L4_CSUM   4u   /* UDP / TCP / ICMP / ICMPv6 checksum, pseudo header where defined   */
+#define PBGPU_WIRE_UDP_LEN   8u   /* a UDP header's length field == its segment's bytes                */
+#define PBGPU_WIRE_ALL      15u
+#define PBGPU_WIRE_MALFORMED 16u  /* code bit only, always checked: a header does not fit or is not what its type says */
+#define PBGPU_WIRE_NOL4      32u  /* info bit: IP, but no level had an L4 checksum that can be evaluated */
+#define PBGPU_WIRE_INNER     64u  /* info bit: a VXLAN inner frame was parsed                          */
+#define PBGPU_WIRE_OTHER    128u  /* info bit: outermost ethertype neither 08 00 nor 86 DD; nothing checked */
+
+typedef struct pbgpu_wire_opts {
+    uint32_t checks;       /* PBGPU_WIRE_* bits 0..3; any other bit: -EINVAL */
+    uint32_t flags;        /* must be 0 */
+    uint16_t vxlan_port;   /* UDP destination port behind which a VXLAN inner frame is looked for; 0 = never */
+    uint16_t reserved[3];  /* must be 0 */
+} pbgpu_wire_opts;
+typedef struct pbgpu_wire_result {
+    uint64_t n_checked, n_bad;      /* n_bad: frames with any of code bits 0..4 */
+    uint64_t bad_malformed, bad_l3_csum, bad_l3_len, bad_l4_csum, bad_udp_len;
+    uint64_t first_bad;             /* lowest bad index into the buffer, UINT64_MAX if none */
+    uint64_t n_ipv4, n_ipv6;        /* by the outermost ethertype (08 00 / 86 DD), malformed or not */
+    uint64_t n_inner, n_nol4, n_other;  /* frames carrying that info bit */
+    double   device_ms;
+} pbgpu_wire_result;
+
+/* A frame's code is the OR of what level(F, 0, L, 0) yields, F its bytes and L its length (the frame
+ * length decides everywhere, never a stored length).  level(F, b, e, depth), for the bytes F[b:e):
+ *   1. Ethernet.  e - b < 14: MALFORMED.  o = b + 12; while o + 2 <= e, BE16(F[o:o+2]) is 0x8100 or
+ *      0x88A8 and fewer than two tags have been skipped: o += 4.  o + 2 > e: MALFORMED.
+ *      et = BE16(F[o:o+2]), l3 = o + 2.
+ *   2. et neither 0x0800 nor 0x86DD: OTHER at depth 0; nothing more is checked at either depth.
+ *   3. IPv4.  MALFORMED if l3 + 20 > e, F[l3] >> 4 != 4, ihl = 4 * (F[l3] & 15) < 20 or l3 + ihl > e.
+ *      L3_CSUM: the ihl header bytes as big-endian words fold to 0xFFFF.  L3_LEN: BE16(F[l3+2:l3+4]) ==
+ *      e - l3.  l4 = l3 + ihl, S = e - l4.  BE16(F[l3+6:l3+8]) & 0x3FFF != 0 is a fragment: no L4 at this
+ *      level.  Otherwise by F[l3+9]:
+ *        UDP (17): S < 8 MALFORMED.  UDP_LEN: BE16(F[l4+4:l4+6]) == S.  A stored checksum 00 00: no L4
+ *          evaluation at this level, not an error.  Else L4_CSUM: pseudo header (source, destination,
+ *          17, S) plus the segment folds to 0xFFFF, an odd last byte padded as the high byte.
+ *        TCP (6): S < 20 MALFORMED; L4_CSUM with the pseudo header of 6; 00 00 gets no special case.
+ *        ICMP (1): S < 8 MALFORMED; L4_CSUM over the segment alone.
+ *        any other protocol: no L4 at this level.
+ *   4. IPv6.  l3 + 40 > e or F[l3] >> 4 != 6: MALFORMED.  L3_LEN: BE16(F[l3+4:l3+6]) == e - l3 - 40.
+ *      l4 = l3 + 40, S = e - l4, nh = F[l3+6].  17: as IPv4's UDP with the RFC 8200 8.1 pseudo header
+ *      (the two addresses, S as 32 bits, nh); a stored 00 00 is an L4_CSUM failure (and counts as an
+ *      evaluation).  6: as IPv4's TCP with that pseudo header.  58 (ICMPv6): S < 4 MALFORMED; L4_CSUM
+ *      with the pseudo header.  Anything else, extension headers included (not walked): no L4.
+ *   5. VXLAN, at depth 0 only: vxlan_port != 0, the level is a non-fragment UDP, BE16(F[l4+2:l4+4]) ==
+ *      vxlan_port, S >= 16 and F[l4+8] & 0x08: INNER, and OR in level(F, l4 + 16, e, 1).  The outer UDP
+ *      checksum is still evaluated when it is not 00 00 (it covers the inner frame).
+ *   6. MALFORMED at a level: that level contributes MALFORMED and none of its other bits, and no deeper
+ *      level is parsed; what an outer level found stays.
+ *   7. NOL4: the frame is not OTHER, no level is malformed and no level reached an L4_CSUM evaluation
+ *      (a fragment, an IPv4 UDP 00 00, an unknown protocol, a non-IP inner frame under an outer 00 00).
+ * The three info bits do not depend on `checks`; failure bits 0..3 appear only where enabled.  Every
+ * header byte these rules read lies in a frame's first 200 bytes (22 + 60 + 8 + 8 + 22 + 60 + 20).
+ * codes_out[j] (host memory, n bytes, or NULL) = the code of frame first_frame + j; first_bad is an
+ * index into the buffer.  Ordered on the context's stream after the build, upload or repack of
+ * `frames`; makes offsets[] present for variable length; returns with the result.  Never writes
+ * frames->data, reads no environment variable, leaves pbgpu_counters alone.  n == 0: a zero result,
+ * first_bad = UINT64_MAX.  A fixed length under 14 is answered on the host (every frame MALFORMED).
+ * -EINVAL: NULL ctx, frames, opts or res; a buffer never built or uploaded; a range past n_frames;
+ * unknown `checks` bits; flags or reserved nonzero. */
+int pbgpu_verify_wire(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uint64_t n,
+                      const pbgpu_wire_opts *opts, pbgpu_wire_result *res, uint8_t *codes_out);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -520,7 +587,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  *        7 sizeof(pbgpu_verify_result), 8 sizeof(pbgpu_pcap_opts), 9 sizeof(pbgpu_encap_opts),
  *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result),
  *        12 sizeof(pbgpu_stamp_opts), 13 sizeof(pbgpu_stamp_result),
- *        14 sizeof(pbgpu_xlat_opts), 15 sizeof(pbgpu_xlat_result);
+ *        14 sizeof(pbgpu_xlat_opts), 15 sizeof(pbgpu_xlat_result),
+ *        16 sizeof(pbgpu_wire_opts), 17 sizeof(pbgpu_wire_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

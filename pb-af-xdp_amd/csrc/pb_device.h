@@ -239,6 +239,24 @@ struct pb_vargs
     uint8_t *codes;          // CODES variants: one code byte per frame of the range
 };
 
+// ---- verification as sent (pbgpu_verify_wire: pb_wire_kernel, pb_wfold_kernel) ----
+// pb_vst_kernel's workgroup, stage and window sizes; a record per workgroup:
+// {bad, malformed, l3 csum, l3 len | l4 csum, udp len, ipv4, ipv6 | inner, nol4, other, 0 | first bad lo, hi, 0, 0}
+#define PB_WREC_DW 16
+struct pb_wargs
+{
+    const uint8_t *data;     // frames->data (16-B aligned)
+    const uint64_t *offsets; // frames->offsets (variable length), null for fixed length
+    uint64_t first, n;       // frames [first, first + n)
+    uint32_t fixed_len;
+    uint32_t checks;         // PBGPU_WIRE_* bits 0..3
+    uint32_t port;           // VXLAN's UDP destination port, 0 = never
+    uint32_t wgf;            // frames per workgroup (a multiple of bf)
+    uint32_t bf;             // frames per stage window (a multiple of PB_VST_WT / G, <= PB_VS_BF_MAX)
+    uint32_t *rec;           // PB_WREC_DW dwords per workgroup
+    uint8_t *codes;          // CODES variants: one code byte per frame of the range
+};
+
 // ---- pcap stream packing (pbgpu_pcap_pack: pb_pcap_kernel) ----
 #define PB_PC_WT 256u                // threads per workgroup: one 16-B chunk each, a 4-KiB page of the stream per step
 #define PB_PC_WIN (PB_PC_WT + 2u)    // records a page can touch (a first partial one + 255 of 16 B, and one more to end the last)

@@ -47,6 +47,8 @@ extern "C" hipError_t pbk_launch_fill(void *dst, uint64_t bytes, int mode, hipSt
 extern "C" const char *pbk_fill_shape_name(int mode);
 extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
+extern "C" hipError_t pbk_launch_wire(const pb_wargs *A, int G, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_wfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
@@ -299,6 +301,7 @@ struct pbgpu_ctx
     uint32_t *d_vfy_rec = nullptr;
     uint64_t vfy_rec_cap = 0; // records
     unsigned long long *h_vres = nullptr, *d_vres = nullptr;
+    unsigned long long *h_wres = nullptr, *d_wres = nullptr; // pbgpu_verify_wire's folded result, as h_vres
     uint8_t *d_vcodes = nullptr;
     uint64_t vcodes_cap = 0;
     // pbgpu_fragment: the count pass's scratch (result words, workgroup sums, K per source frame)
@@ -828,6 +831,8 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipFree(ctx->d_vfy_rec);
     if (ctx->h_vres)
         (void)hipHostFree(ctx->h_vres);
+    if (ctx->h_wres)
+        (void)hipHostFree(ctx->h_wres);
     if (ctx->d_vcodes)
         (void)hipFree(ctx->d_vcodes);
     if (ctx->d_fg_cnt)
@@ -2416,6 +2421,26 @@ int pbgpu_copy_offsets(pbgpu_ctx *ctx, const pbgpu_frames *f, uint64_t *dst)
 
 // ---- verification ----
 
+// pb_vst_kernel's (and pb_wire_kernel's) launch of n frames of mean length `mean`: G lanes per frame,
+// frames per workgroup and per stage window
+static int vst_shape(const pbgpu_frames *f, uint64_t n, uint64_t mean, uint32_t *wgf, uint32_t *bf_out,
+                     uint32_t *grid)
+{
+    const int G = mean <= 192 ? 8 : (mean <= 768 ? 16 : (mean <= 3072 ? 32 : 64));
+    const uint32_t ng = PB_VST_WT / (uint32_t)G;
+    // a window fills the stage (fixed length), or three quarters of it: a variable-length window of
+    // longer frames then still fits (one that does not is summed from global memory)
+    const uint64_t target = f->fixed_len ? PB_VS_STAGE - 16 : PB_VS_STAGE / 4 * 3;
+    uint64_t bf = target / (mean ? mean : 1) / ng * ng;
+    bf = bf < ng ? ng : (bf > PB_VS_BF_MAX ? PB_VS_BF_MAX : bf);
+    uint64_t nw = n / (bf * 16384); // windows per workgroup
+    nw = nw < 1 ? 1 : (nw > 64 ? 64 : nw);
+    *bf_out = (uint32_t)bf;
+    *wgf = (uint32_t)(bf * nw);
+    *grid = (uint32_t)((n + *wgf - 1) / *wgf);
+    return G;
+}
+
 // The verify launch of frames [first, first + n): pb_vpg_kernel for fixed lengths up to 128 B,
 // pb_vst_kernel with G lanes per frame by the mean length otherwise.
 static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint64_t mean, pb_vargs *A, uint32_t *grid)
@@ -2430,19 +2455,7 @@ static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint6
         (void)page_grid(A->npages, &A->wgf, grid);
         return 0;
     }
-    const int G = mean <= 192 ? 8 : (mean <= 768 ? 16 : (mean <= 3072 ? 32 : 64));
-    const uint32_t ng = PB_VST_WT / (uint32_t)G;
-    // a window fills the stage (fixed length), or three quarters of it: a variable-length window of
-    // longer frames then still fits (one that does not is summed from global memory)
-    const uint64_t target = f->fixed_len ? PB_VS_STAGE - 16 : PB_VS_STAGE / 4 * 3;
-    uint64_t bf = target / (mean ? mean : 1) / ng * ng;
-    bf = bf < ng ? ng : (bf > PB_VS_BF_MAX ? PB_VS_BF_MAX : bf);
-    uint64_t nw = n / (bf * 16384); // windows per workgroup
-    nw = nw < 1 ? 1 : (nw > 64 ? 64 : nw);
-    A->bf = (uint32_t)bf;
-    A->wgf = (uint32_t)(bf * nw);
-    *grid = (uint32_t)((n + A->wgf - 1) / A->wgf);
-    return G;
+    return vst_shape(f, n, mean, &A->wgf, &A->bf, grid);
 }
 
 int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, uint32_t checks,
@@ -2514,6 +2527,91 @@ int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t
     res->bad_tot_len = ctx->h_vres[3];
     res->bad_l4_csum = ctx->h_vres[4];
     res->first_bad = ctx->h_vres[5];
+    res->device_ms = ms;
+    return PBGPU_OK;
+}
+
+// ---- verification as sent ----
+
+int pbgpu_verify_wire(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, const pbgpu_wire_opts *opts,
+                      pbgpu_wire_result *res, uint8_t *codes_out)
+{
+    if (ctx == NULL || f == NULL || opts == NULL || res == NULL || !frames_range_ok(f, first_frame, n))
+        return PBGPU_EINVAL;
+    if ((opts->checks & ~PBGPU_WIRE_ALL) || opts->flags || opts->reserved[0] || opts->reserved[1] || opts->reserved[2])
+        return PBGPU_EINVAL;
+    memset(res, 0, sizeof *res);
+    res->first_bad = UINT64_MAX;
+    if (n == 0)
+        return PBGPU_OK;
+    res->n_checked = n;
+    if (f->fixed_len && f->fixed_len < 14) // no frame holds an Ethernet header: nothing to read
+    {
+        res->n_bad = res->bad_malformed = n;
+        res->first_bad = first_frame;
+        if (codes_out)
+            memset(codes_out, PBGPU_WIRE_MALFORMED, n);
+        return PBGPU_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    uint64_t mean = f->fixed_len;
+    if (!f->fixed_len)
+    {
+        const int mrc = materialize_offsets(ctx, f);
+        if (mrc != PBGPU_OK)
+            return mrc;
+        uint64_t total = 0;
+        const int trc = pbgpu_frames_total(ctx, f, &total);
+        if (trc != PBGPU_OK)
+            return trc;
+        mean = total / f->n_frames;
+    }
+    pb_wargs A;
+    memset(&A, 0, sizeof A);
+    A.data = f->data;
+    A.offsets = f->fixed_len ? nullptr : f->offsets;
+    A.first = first_frame;
+    A.n = n;
+    A.fixed_len = f->fixed_len;
+    A.checks = opts->checks;
+    A.port = opts->vxlan_port;
+    uint32_t grid = 0;
+    const int G = vst_shape(f, n, mean, &A.wgf, &A.bf, &grid);
+    // pbgpu_verify's record buffer, counted in its records: one of this kernel's is two of them
+    PBCHK(scratch_reserve((void **)&ctx->d_vfy_rec, &ctx->vfy_rec_cap, (uint64_t)grid * 2,
+                          (size_t)grid * PB_WREC_DW * sizeof(uint32_t)));
+    if (ctx->h_wres == nullptr)
+    {
+        HIPCHK(hipHostMalloc((void **)&ctx->h_wres, 12 * sizeof(unsigned long long),
+                             hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_wres, ctx->h_wres, 0));
+    }
+    if (codes_out)
+        PBCHK(scratch_reserve((void **)&ctx->d_vcodes, &ctx->vcodes_cap, n, n));
+    A.rec = ctx->d_vfy_rec;
+    A.codes = codes_out ? ctx->d_vcodes : nullptr;
+    timing_pair tp;
+    PBCHK(timed_begin(ctx, &tp));
+    HIPCHK(pbk_launch_wire(&A, G, grid, ctx->stream));
+    HIPCHK(pbk_launch_wfold(ctx->d_vfy_rec, grid, ctx->d_wres, ctx->stream));
+    PBCHK(timed_stop(ctx, tp));
+    if (codes_out) // after the timed stretch
+        HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
+    float ms = 0;
+    PBCHK(timed_ms(ctx, tp, &ms));
+    res->n_bad = ctx->h_wres[0];
+    res->bad_malformed = ctx->h_wres[1];
+    res->bad_l3_csum = ctx->h_wres[2];
+    res->bad_l3_len = ctx->h_wres[3];
+    res->bad_l4_csum = ctx->h_wres[4];
+    res->bad_udp_len = ctx->h_wres[5];
+    res->n_ipv4 = ctx->h_wres[6];
+    res->n_ipv6 = ctx->h_wres[7];
+    res->n_inner = ctx->h_wres[8];
+    res->n_nol4 = ctx->h_wres[9];
+    res->n_other = ctx->h_wres[10];
+    res->first_bad = ctx->h_wres[11];
     res->device_ms = ms;
     return PBGPU_OK;
 }
@@ -3742,6 +3840,8 @@ size_t pbgpu_abi_size(int which)
     case 13: return sizeof(pbgpu_stamp_result);
     case 14: return sizeof(pbgpu_xlat_opts);
     case 15: return sizeof(pbgpu_xlat_result);
+    case 16: return sizeof(pbgpu_wire_opts);
+    case 17: return sizeof(pbgpu_wire_result);
     default: return 0;
     }
 }

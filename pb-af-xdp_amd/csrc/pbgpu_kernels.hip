@@ -4278,6 +4278,452 @@ extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t 
     return hipGetLastError();
 }
 
+// ======================= verification as sent (pbgpu_verify_wire) =======================
+// pb_vst_kernel's scaffolding with the offsets as data: where the L3 and L4 headers lie is read from
+// the frame (up to two VLAN tags, IPv4 with options or IPv6, one VXLAN inner frame), see pbgpu.h.
+// Per window a parse stage - one lane per frame - walks the headers out of LDS, sums the IPv4
+// header(s) and the pseudo header(s) itself and leaves a two-dword descriptor; the sum stage then
+// takes a frame per group of G lanes as pb_vst_kernel does, for up to two ranges that both end at
+// the frame's end.  All header positions are even relative to the frame's start, so the parse
+// lane's sums are in the frame domain like pb_vst_kernel's.
+
+// descriptor word 0: the code so far (PB_W_* bits), range 0's start at bits 16-23, range 1's at
+// 24-31 (bytes from the frame's start, 0 = no range; an L4 header starts at byte 34 or later and,
+// by the 200-byte bound of pbgpu.h, before byte 181); word 1: the folded partial sums the ranges'
+// folds must meet, 16 bits each
+#define PB_W_V4 0x100u   // outermost ethertype 08 00
+#define PB_W_V6 0x200u   // outermost ethertype 86 DD
+#define PB_W_EVAL 0x400u // some level reached an L4 checksum evaluation
+
+__device__ __forceinline__ uint32_t pb_wbe16(const uint32_t *dw, uint32_t byte)
+{
+    return pb_bswap16(pb_vdw(dw, byte));
+}
+
+// hb: the frame's first byte in the LDS area dw; len: its length
+__device__ __forceinline__ uint2 pb_wire_parse(const uint32_t *dw, uint32_t hb, uint32_t len, uint32_t port,
+                                               uint32_t checks)
+{
+    uint32_t code = 0, lo0 = 0, lo1 = 0, ps0 = 0, ps1 = 0;
+    uint32_t b = 0;
+    for (uint32_t depth = 0; depth < 2u; ++depth)
+    {
+        uint32_t lv = 0, rlo = 0, rps = 0, nb = 0;
+        bool mal = false, eval = false;
+        do
+        {
+            if (len - b < 14u)
+            {
+                mal = true;
+                break;
+            }
+            uint32_t o = b + 12u;
+            uint32_t et = pb_wbe16(dw, hb + o);
+            for (uint32_t t = 0; t < 2u && (et == 0x8100u || et == 0x88A8u); ++t)
+            {
+                o += 4u;
+                if (o + 2u > len)
+                {
+                    mal = true;
+                    break;
+                }
+                et = pb_wbe16(dw, hb + o);
+            }
+            if (mal)
+                break;
+            const uint32_t l3 = o + 2u;
+            uint32_t l4, proto, pseudo = 0;
+            bool v6 = false, frag = false;
+            if (et == 0x0800u)
+            {
+                if (depth == 0u)
+                    code |= PB_W_V4;
+                if (l3 + 20u > len)
+                {
+                    mal = true;
+                    break;
+                }
+                const uint32_t w0 = pb_vdw(dw, hb + l3); // version / IHL, TOS, tot_len
+                const uint32_t ihl = 4u * (w0 & 15u);
+                if (((w0 >> 4) & 15u) != 4u || ihl < 20u || l3 + ihl > len)
+                {
+                    mal = true;
+                    break;
+                }
+                uint32_t s = 0;
+                for (uint32_t k = 0; k < ihl; k += 4u)
+                    s = pb_add_halves(s, pb_vdw(dw, hb + l3 + k));
+                if (pb_fold(s) != 0xFFFFu)
+                    lv |= 1u;
+                if (pb_bswap16(w0 >> 16) != len - l3)
+                    lv |= 2u;
+                const uint32_t w2 = pb_vdw(dw, hb + l3 + 6u); // fragment field, TTL, protocol
+                frag = (pb_bswap16(w2) & 0x3FFFu) != 0u;
+                proto = w2 >> 24;
+                pseudo = pb_add_halves(pb_add_halves(0u, pb_vdw(dw, hb + l3 + 12u)), pb_vdw(dw, hb + l3 + 16u));
+                l4 = l3 + ihl;
+            }
+            else if (et == 0x86DDu)
+            {
+                if (depth == 0u)
+                    code |= PB_W_V6;
+                if (l3 + 40u > len || ((pb_vdw(dw, hb + l3) >> 4) & 15u) != 6u)
+                {
+                    mal = true;
+                    break;
+                }
+                const uint32_t w1 = pb_vdw(dw, hb + l3 + 4u); // payload length, next header, hop limit
+                if (pb_bswap16(w1) != len - l3 - 40u)
+                    lv |= 2u;
+                proto = (w1 >> 16) & 0xFFu;
+                for (uint32_t k = 8u; k < 40u; k += 4u)
+                    pseudo = pb_add_halves(pseudo, pb_vdw(dw, hb + l3 + k));
+                l4 = l3 + 40u;
+                v6 = true;
+            }
+            else
+            {
+                if (depth == 0u)
+                    code |= 128u;
+                break;
+            }
+            if (frag)
+                break;
+            const uint32_t S = len - l4;
+            // the pseudo header's protocol word and length (below 2^16), frame domain
+            const uint32_t pfull = pb_fold(pseudo + (proto << 8) + pb_bswap16(S));
+            if (proto == 17u)
+            {
+                if (S < 8u)
+                {
+                    mal = true;
+                    break;
+                }
+                const uint32_t u0 = pb_vdw(dw, hb + l4), u1 = pb_vdw(dw, hb + l4 + 4u);
+                if (pb_bswap16(u1) != S)
+                    lv |= 8u;
+                if ((u1 >> 16) == 0u)
+                {
+                    if (v6) // RFC 8200 8.1: no UDP over IPv6 without a checksum
+                        lv |= 4u, eval = true;
+                }
+                else
+                    rlo = l4, rps = pfull, eval = true;
+                if (depth == 0u && port != 0u && pb_bswap16(u0 >> 16) == port && S >= 16u &&
+                    (pb_vdw(dw, hb + l4 + 8u) & 0x08u))
+                {
+                    code |= 64u;
+                    nb = l4 + 16u;
+                }
+            }
+            else if (proto == 6u)
+            {
+                if (S < 20u)
+                {
+                    mal = true;
+                    break;
+                }
+                rlo = l4, rps = pfull, eval = true;
+            }
+            else if (!v6 && proto == 1u)
+            {
+                if (S < 8u)
+                {
+                    mal = true;
+                    break;
+                }
+                rlo = l4, rps = 0u, eval = true;
+            }
+            else if (v6 && proto == 58u)
+            {
+                if (S < 4u)
+                {
+                    mal = true;
+                    break;
+                }
+                rlo = l4, rps = pfull, eval = true;
+            }
+        } while (false);
+        if (mal) // this level gives MALFORMED alone; what the outer level found stays
+        {
+            code |= 16u;
+            break;
+        }
+        code |= (lv & checks) | (eval ? PB_W_EVAL : 0u);
+        if (rlo)
+        {
+            if (lo0 == 0u)
+                lo0 = rlo, ps0 = rps;
+            else
+                lo1 = rlo, ps1 = rps;
+        }
+        if (nb == 0u)
+            break;
+        b = nb;
+    }
+    if (!(code & (128u | 16u | PB_W_EVAL)))
+        code |= 32u;
+    return make_uint2(code | lo0 << 16 | lo1 << 24, ps0 | ps1 << 16);
+}
+
+// a wave's tallies (the counts are wave-uniform, first is per lane); code: PB_W_* included
+struct pb_wcount
+{
+    uint32_t c[11]; // bad, malformed, l3 csum, l3 len, l4 csum, udp len, ipv4, ipv6, inner, nol4, other
+    uint64_t first;
+};
+
+__device__ __forceinline__ void pb_wtally(pb_wcount &c, bool lead, uint32_t code, uint64_t f)
+{
+    if (__ballot(lead && (code & 31u))) // wave-uniform: clean frames skip the failure counts
+    {
+        c.c[0] += (uint32_t)__popcll(__ballot(lead && (code & 31u)));
+        c.c[1] += (uint32_t)__popcll(__ballot(lead && (code & 16u)));
+        c.c[2] += (uint32_t)__popcll(__ballot(lead && (code & 1u)));
+        c.c[3] += (uint32_t)__popcll(__ballot(lead && (code & 2u)));
+        c.c[4] += (uint32_t)__popcll(__ballot(lead && (code & 4u)));
+        c.c[5] += (uint32_t)__popcll(__ballot(lead && (code & 8u)));
+        if (lead && (code & 31u) && f < c.first)
+            c.first = f;
+    }
+    c.c[6] += (uint32_t)__popcll(__ballot(lead && (code & PB_W_V4)));
+    c.c[7] += (uint32_t)__popcll(__ballot(lead && (code & PB_W_V6)));
+    c.c[8] += (uint32_t)__popcll(__ballot(lead && (code & 64u)));
+    c.c[9] += (uint32_t)__popcll(__ballot(lead && (code & 32u)));
+    c.c[10] += (uint32_t)__popcll(__ballot(lead && (code & 128u)));
+}
+
+template <int G, bool CODES>
+__global__ __launch_bounds__(PB_VST_WT) void pb_wire_kernel(pb_wargs A)
+{
+    constexpr uint32_t NG = PB_VST_WT / G, NWV = PB_VST_WT / 64;
+    __shared__ pb_u32x4 s_stage[(PB_VS_STAGE + PB_VS_SLACK) / 16];
+    __shared__ uint32_t s_off[PB_VS_BF_MAX + 1];
+    __shared__ uint2 s_desc[PB_VS_BF_MAX];
+    __shared__ uint32_t s_cnt[NWV][PB_WREC_DW];
+    const uint32_t *dw = reinterpret_cast<const uint32_t *>(s_stage);
+    const uint32_t tid = threadIdx.x, grp = tid / G, gl = tid % G;
+    const uint64_t fa = (uint64_t)pb_xcd_region(blockIdx.x, gridDim.x) * A.wgf;
+    const uint64_t fe = fa + A.wgf < A.n ? fa + A.wgf : A.n;
+    pb_wcount c = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ~0ull};
+    for (uint64_t w0 = fa; w0 < fe; w0 += A.bf)
+    {
+        const uint32_t wn = fe - w0 < A.bf ? (uint32_t)(fe - w0) : A.bf;
+        const uint64_t g0 = A.first + w0;
+        const uint64_t sb = A.offsets ? A.offsets[g0] : g0 * A.fixed_len;
+        const uint64_t eb = A.offsets ? A.offsets[g0 + wn] : (g0 + wn) * A.fixed_len;
+        const uint64_t s16 = sb & ~15ull;
+        const bool staged = eb - s16 <= PB_VS_STAGE;
+        const uint32_t span16 = (uint32_t)((eb - s16 + 15ull) & ~15ull); // < 2^26: bf frames of < 64 KiB
+        const uint8_t *src = A.data + s16;
+        if (w0 != fa)
+            __syncthreads(); // the previous window has been summed
+        for (uint32_t i = tid; i <= wn; i += PB_VST_WT)
+            s_off[i] = (uint32_t)((A.offsets ? A.offsets[g0 + i] : (g0 + i) * A.fixed_len) - s16);
+        if (staged)
+            for (uint32_t ch = tid; ch < (span16 >> 4); ch += PB_VST_WT)
+                s_stage[ch] = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
+        __syncthreads();
+        if (staged)
+        {
+            // parse stage: one lane per frame of the window
+            for (uint32_t i = tid; i < wn; i += PB_VST_WT)
+                s_desc[i] = pb_wire_parse(dw, s_off[i], s_off[i + 1u] - s_off[i], A.port, A.checks);
+            __syncthreads();
+        }
+        for (uint32_t r0 = 0; r0 < wn; r0 += NG)
+        {
+            const uint32_t fi = r0 + grp;
+            const bool valid = fi < wn;
+            const uint32_t p = s_off[valid ? fi : 0u], q = s_off[valid ? fi + 1u : 0u];
+            if (!staged)
+            {
+                // the frame's first fourteen chunks (every header byte lies in its first 200 bytes) into
+                // the group's 224-B slot, parsed by the group's first lane (a group is inside one wave)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (uint32_t k = gl; k < 14u; k += G)
+                {
+                    const uint32_t cb = (p & ~15u) + 16u * k;
+                    s_stage[grp * 14u + k] =
+                        cb < span16 ? *reinterpret_cast<const pb_u32x4 *>(src + cb) : pb_u32x4{0, 0, 0, 0};
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (valid && gl == 0u)
+                    s_desc[fi] = pb_wire_parse(dw, grp * 224u + (p & 15u), q - p, A.port, A.checks);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            const uint2 d = s_desc[valid ? fi : 0u];
+            const uint32_t r0lo = (d.x >> 16) & 0xFFu, r1lo = d.x >> 24;
+            uint32_t acc0 = 0, acc1 = 0;
+            if (valid && r0lo)
+            {
+                const uint32_t lo = p + r0lo, hi = q; // hi > lo: an L4 header fits
+                const uint32_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
+                // Range 1 is there only for a VXLAN frame whose outer UDP checksum is not 00 00: the outer
+                // range then contains the inner one, and the inner bytes are added to both sums from the one
+                // load.  No pipeline of this generator produces that case (pbgpu_encap writes 00 00); it comes
+                // from uploads only.
+                const uint32_t lo1 = p + r1lo, c0b = r1lo ? lo1 >> 4 : ~0u;
+                for (uint32_t ch = c0 + gl; ch <= c1; ch += G)
+                {
+                    pb_u32x4 v;
+                    if (staged)
+                        v = s_stage[ch];
+                    else
+                        v = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
+                    if (ch == c0 || ch == c1)
+                    {
+                        const int a = (int)lo - (int)(16u * ch), b = (int)hi - (int)(16u * ch);
+                        v.x &= pb_bytemask(a, b, 0);
+                        v.y &= pb_bytemask(a, b, 1);
+                        v.z &= pb_bytemask(a, b, 2);
+                        v.w &= pb_bytemask(a, b, 3);
+                    }
+                    acc0 = pb_add_halves(acc0, v.x);
+                    acc0 = pb_add_halves(acc0, v.y);
+                    acc0 = pb_add_halves(acc0, v.z);
+                    acc0 = pb_add_halves(acc0, v.w);
+                    if (ch >= c0b)
+                    {
+                        if (ch == c0b)
+                        {
+                            const int a = (int)lo1 - (int)(16u * ch);
+                            v.x &= pb_bytemask(a, 16, 0);
+                            v.y &= pb_bytemask(a, 16, 1);
+                            v.z &= pb_bytemask(a, 16, 2);
+                            v.w &= pb_bytemask(a, 16, 3);
+                        }
+                        acc1 = pb_add_halves(acc1, v.x);
+                        acc1 = pb_add_halves(acc1, v.y);
+                        acc1 = pb_add_halves(acc1, v.z);
+                        acc1 = pb_add_halves(acc1, v.w);
+                    }
+                }
+            }
+            acc0 = pb_group_sum<G>(acc0);
+            acc1 = pb_group_sum<G>(acc1);
+            uint32_t seg0 = pb_fold(acc0), seg1 = pb_fold(acc1);
+            if (p & 1u) // the sums were taken on the buffer's even addresses (s16 is even)
+                seg0 = pb_bswap16(seg0), seg1 = pb_bswap16(seg1);
+            const bool lead = valid && gl == 0u;
+            uint32_t code = lead ? d.x & 0x7FFu : 0u;
+            if (lead && r0lo && pb_fold(seg0 + (d.y & 0xFFFFu)) != 0xFFFFu)
+                code |= 4u & A.checks;
+            if (lead && r1lo && pb_fold(seg1 + (d.y >> 16)) != 0xFFFFu)
+                code |= 4u & A.checks;
+            pb_wtally(c, lead, code, g0 + fi);
+            if (CODES && lead)
+                A.codes[w0 + fi] = (uint8_t)code;
+        }
+    }
+    const uint64_t first = pb_vwave_min(c.first);
+    if ((tid & 63u) == 0)
+    {
+        uint32_t *r = s_cnt[tid >> 6];
+#pragma unroll
+        for (uint32_t k = 0; k < 11u; ++k)
+            r[k] = c.c[k];
+        r[12] = (uint32_t)first, r[13] = (uint32_t)(first >> 32);
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        uint32_t t[11];
+        uint64_t mn = ~0ull;
+#pragma unroll
+        for (uint32_t k = 0; k < 11u; ++k)
+        {
+            t[k] = 0;
+            for (uint32_t w = 0; w < NWV; ++w)
+                t[k] += s_cnt[w][k];
+        }
+        for (uint32_t w = 0; w < NWV; ++w)
+        {
+            const uint64_t m = s_cnt[w][12] | (uint64_t)s_cnt[w][13] << 32;
+            mn = m < mn ? m : mn;
+        }
+        // the workgroup's record: four plain 16-B stores
+        pb_u32x4 *r = reinterpret_cast<pb_u32x4 *>(A.rec + (size_t)blockIdx.x * PB_WREC_DW);
+        r[0] = pb_u32x4{t[0], t[1], t[2], t[3]};
+        r[1] = pb_u32x4{t[4], t[5], t[6], t[7]};
+        r[2] = pb_u32x4{t[8], t[9], t[10], 0u};
+        r[3] = pb_u32x4{(uint32_t)mn, (uint32_t)(mn >> 32), 0u, 0u};
+    }
+}
+
+// The workgroups' records folded by one workgroup into mapped pinned host memory, as pb_vfold_kernel
+// does: out = the eleven counts in the record's order, then the first bad index
+__global__ __launch_bounds__(256) void pb_wfold_kernel(const uint32_t *rec, uint32_t nrec, unsigned long long *out)
+{
+    uint64_t t[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mn = ~0ull;
+    for (uint32_t i = threadIdx.x; i < nrec; i += 256u)
+    {
+        const pb_u32x4 *r = reinterpret_cast<const pb_u32x4 *>(rec + (size_t)i * PB_WREC_DW);
+        const pb_u32x4 a = r[0], b = r[1], cc = r[2], d = r[3];
+        t[0] += a.x, t[1] += a.y, t[2] += a.z, t[3] += a.w;
+        t[4] += b.x, t[5] += b.y, t[6] += b.z, t[7] += b.w;
+        t[8] += cc.x, t[9] += cc.y, t[10] += cc.z;
+        const uint64_t m = d.x | (uint64_t)d.y << 32;
+        mn = m < mn ? m : mn;
+    }
+#pragma unroll
+    for (uint32_t dd = 32; dd > 0; dd >>= 1)
+#pragma unroll
+        for (uint32_t k = 0; k < 11; ++k)
+            t[k] += __shfl_xor(t[k], dd, 64);
+    mn = pb_vwave_min(mn);
+    __shared__ unsigned long long s_t[4][12];
+    if ((threadIdx.x & 63u) == 0)
+    {
+#pragma unroll
+        for (uint32_t k = 0; k < 11; ++k)
+            s_t[threadIdx.x >> 6][k] = t[k];
+        s_t[threadIdx.x >> 6][11] = mn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        for (uint32_t k = 0; k < 11; ++k)
+            out[k] = s_t[0][k] + s_t[1][k] + s_t[2][k] + s_t[3][k];
+        for (uint32_t w = 1; w < 4; ++w)
+            mn = s_t[w][11] < mn ? s_t[w][11] : mn;
+        out[11] = mn;
+    }
+}
+
+// G: lanes per frame (8, 16, 32, 64)
+extern "C" hipError_t pbk_launch_wire(const pb_wargs *A, int G, uint32_t grid, hipStream_t st)
+{
+    const bool codes = A->codes != nullptr;
+#define PBK_WIRE(G)                                                                              \
+    if (codes)                                                                                   \
+        hipLaunchKernelGGL((pb_wire_kernel<G, true>), dim3(grid), dim3(PB_VST_WT), 0, st, *A);    \
+    else                                                                                         \
+        hipLaunchKernelGGL((pb_wire_kernel<G, false>), dim3(grid), dim3(PB_VST_WT), 0, st, *A);
+    switch (G)
+    {
+    case 8: PBK_WIRE(8) break;
+    case 16: PBK_WIRE(16) break;
+    case 32: PBK_WIRE(32) break;
+    case 64: PBK_WIRE(64) break;
+    default: return hipErrorInvalidValue;
+    }
+#undef PBK_WIRE
+    return hipGetLastError();
+}
+
+extern "C" hipError_t pbk_launch_wfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(pb_wfold_kernel, dim3(1), dim3(256), 0, st, rec, nrec, out);
+    return hipGetLastError();
+}
+
 // ---------------- repack helpers (pcap pack, encap, fragment: DESIGN.md 5.9-5.11) ----------------
 // The three writers are destination-owned: a workgroup owns consecutive 4-KiB pages of the output, a
 // lane one aligned 16-B chunk of a page per step.  Output record j is source frame first + j with

@@ -50,6 +50,8 @@ static int stamp_twice;
 /* --xlat6 SRC6/96[,DST6/96][:hashflow], once: handed to the driver with pb_set_xlat */
 static const char *xlat_spec;
 static int xlat_twice;
+/* --verifywire: handed to the driver with pb_set_verify_wire */
+static int verify_wire;
 
 static void sign_hdl(int sig)
 {
@@ -63,7 +65,7 @@ enum
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
     O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT, O_STAMP,
-    O_XLAT6,
+    O_XLAT6, O_VERIFYWIRE,
 };
 
 static const struct option common_opts[] = {
@@ -105,6 +107,7 @@ static const struct option common_opts[] = {
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
     {"encap", required_argument, NULL, O_ENCAP}, {"fragment", required_argument, NULL, O_FRAGMENT},
     {"stamp", required_argument, NULL, O_STAMP}, {"xlat6", required_argument, NULL, O_XLAT6},
+    {"verifywire", no_argument, NULL, O_VERIFYWIRE},
     {NULL, 0, NULL, 0},
 };
 
@@ -209,6 +212,7 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
                 xlat_twice = 1;
             xlat_spec = a;
             break;
+        case O_VERIFYWIRE: verify_wire = 1; break;
         default: break;
         }
     }
@@ -456,8 +460,14 @@ static void print_cmd_help(void)
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
                     "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf] "
-                    "--stamp head[:OFF]|tail[:OFF] --xlat6 SRC6/96[,DST6/96][:hashflow]\n"
-                    "--verify => Check every built batch's checksums and lengths on the GPU before it is sent.\n"
+                    "--stamp head[:OFF]|tail[:OFF] --xlat6 SRC6/96[,DST6/96][:hashflow] --verifywire\n"
+                    "--verify => Check every built batch's checksums and lengths on the GPU as it is built (and stamped): "
+                    "Ethernet + IPv4 without options. Of a repacked batch it sees the IPv4 checksum and length of "
+                    "fragments and of a VXLAN outer header, nothing of a VLAN or IPv6 frame.\n"
+                    "--verifywire => Check every batch on the GPU as it leaves, after the last repack: VLAN tags, IPv4 "
+                    "or IPv6, a VXLAN inner frame, fragments and UDP without a checksum are told from the frames' own "
+                    "bytes. One more line at the end; a bad frame stops the sequence as --verify's does. May be given "
+                    "beside --verify.\n"
                     "--pcapdump FILE => Write the sequences' frames (--maxpckts each) to FILE as a pcap capture packed "
                     "on the GPU; nothing is sent. Timestamps: --pcapt0 NS (ns since the epoch, default now) plus "
                     "1/pps per frame.\n"
@@ -578,6 +588,7 @@ int main(int argc, char **argv)
         }
         pb_set_xlat(&xo);
     }
+    pb_set_verify_wire(verify_wire);
     struct cmd_line_af_xdp cmd_af_xdp = {0};
     cmd_line_af_xdp_defaults(&cmd_af_xdp);
     optind = 0; /* main.c:45 */
@@ -634,6 +645,8 @@ int main(int argc, char **argv)
             inet_ntop(AF_INET6, a, d6, sizeof d6);
             fprintf(stdout, "XLAT6: src=%s/96 dst=%s/96 hashflow=%u\n", s6, d6, xo->flags & PBGPU_XLAT_HASH_FLOW);
         }
+        if (pb_get_verify_wire())
+            fprintf(stdout, "VERIFYWIRE: on\n");
         for (int i = 0; i < seq_cnt; ++i)
             fprintf(stdout, "Sequence #%d: %s -> %s proto %s, %u payload(s)\n", i + 1,
                     cfg->seq[i].ip.src_ip ? cfg->seq[i].ip.src_ip

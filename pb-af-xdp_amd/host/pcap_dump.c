@@ -85,7 +85,8 @@ typedef struct dump_state
 
 /* One sequence: frames [0, max_pckts) stamped from t0_ns; *n_done = the frames written. */
 static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx, uint64_t t0_ns, uint64_t step_ps,
-                         uint64_t *n_done, uint64_t *n_verified, uint64_t *n_bad, uint64_t *n_packed, uint64_t *b_packed)
+                         uint64_t *n_done, uint64_t *n_verified, uint64_t *n_bad, uint64_t *n_packed, uint64_t *b_packed,
+                         pb_wire_tally_t *wire)
 {
     const int seq_num = idx + 1;
     pbgpu_ctx *ctx = D->ctx;
@@ -262,6 +263,25 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
                     pbgpu_strerror(rc), rc == PBGPU_EINVAL ? " (a frame too long for the outer header?)" : "");
             goto out;
         }
+        if (pb_get_verify_wire()) /* --verifywire: the batch as it is packed, after the last repack */
+        {
+            pbgpu_wire_opts wo;
+            pbgpu_wire_result wr;
+            pb_wire_opts_for(seq, &wo);
+            if ((rc = pbgpu_verify_wire(ctx, encap ? enc : bf, 0, btake, &wo, &wr, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error verifying frames as sent on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc));
+                goto out;
+            }
+            pb_wire_tally_add(wire, &wr);
+            if (wr.n_bad)
+            {
+                pb_verify_wire_failed_msg(seq_num, wr.n_bad, wr.first_bad, iter);
+                rc = PBGPU_EIO;
+                goto out;
+            }
+        }
         pbgpu_pcap_opts o;
         memset(&o, 0, sizeof o);
         o.t0_ns = t0_ns;
@@ -363,6 +383,8 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
     uint64_t verified[PB_MAX_SEQUENCES] = {0}, bad[PB_MAX_SEQUENCES] = {0}, written[PB_MAX_SEQUENCES] = {0};
     uint64_t packed[PB_MAX_SEQUENCES] = {0}, packed_b[PB_MAX_SEQUENCES] = {0};
     time_t secs[PB_MAX_SEQUENCES] = {0};
+    pb_wire_tally_t wire[PB_MAX_SEQUENCES];
+    memset(wire, 0, sizeof wire);
     int ran = 0;
     for (int i = 0; i < seq_cnt && rc == 0 && !pb_stop_requested(); ++i)
     {
@@ -376,7 +398,8 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
         const uint64_t step_ps = seq->pps > 0 ? 1000000000000ull / seq->pps : 0;
         uint64_t n = 0;
         const time_t t_start = time(NULL);
-        rc = dump_sequence(&D, seq, (uint16_t)i, t0_ns, step_ps, &n, &verified[i], &bad[i], &packed[i], &packed_b[i]);
+        rc = dump_sequence(&D, seq, (uint16_t)i, t0_ns, step_ps, &n, &verified[i], &bad[i], &packed[i], &packed_b[i],
+                           &wire[i]);
         secs[i] = time(NULL) - t_start;
         /* the next sequence continues where this one's clock stopped */
         t0_ns += (uint64_t)((unsigned __int128)packed[i] * step_ps / 1000u);
@@ -415,6 +438,8 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
     }
     for (int i = 0; i < ran && cmd->verify; ++i)
         pb_print_verified(verified[i], bad[i]);
+    for (int i = 0; i < ran && pb_get_verify_wire(); ++i)
+        pb_print_verified_wire(&wire[i]);
     fflush(stdout);
     pbgpu_close(D.ctx);
     return rc;

@@ -70,6 +70,9 @@ static pbgpu_stamp_opts stamp_opts;
 static uint64_t stamp_t0[PB_MAX_SEQUENCES]; /* t0 of each sequence: --pcapt0, else the clock at its start */
 static int xlat_on; /* --xlat6 (pb_set_xlat) */
 static pbgpu_xlat_opts xlat_opts;
+static int vwire_on; /* --verifywire (pb_set_verify_wire) */
+static uint8_t vwire_seq[PB_MAX_SEQUENCES]; /* the sequences that ran with it: they get the line */
+static pb_wire_tally_t vwire_tally[PB_MAX_SEQUENCES];
 
 void pb_request_stop(void)
 {
@@ -139,6 +142,36 @@ void pb_set_xlat(const pbgpu_xlat_opts *opts)
 const pbgpu_xlat_opts *pb_get_xlat(void)
 {
     return xlat_on ? &xlat_opts : NULL;
+}
+
+void pb_set_verify_wire(int on)
+{
+    vwire_on = on != 0;
+}
+
+int pb_get_verify_wire(void)
+{
+    return vwire_on;
+}
+
+void pb_wire_opts_for(const pb_sequence_t *seq, pbgpu_wire_opts *opts)
+{
+    memset(opts, 0, sizeof *opts);
+    opts->checks = (seq->ip.csum ? PBGPU_WIRE_L3_CSUM | PBGPU_WIRE_L3_LEN : 0u) | (xlat_on ? PBGPU_WIRE_L3_LEN : 0u) |
+                   (seq->l4_csum ? PBGPU_WIRE_L4_CSUM : 0u) | PBGPU_WIRE_UDP_LEN;
+    if (encap_on && encap_opts.mode == PBGPU_ENCAP_VXLAN)
+        opts->vxlan_port = encap_opts.dst_port ? encap_opts.dst_port : 4789;
+}
+
+void pb_wire_tally_add(pb_wire_tally_t *t, const pbgpu_wire_result *r)
+{
+    __atomic_add_fetch(&t->frames, r->n_checked, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->bad, r->n_bad, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->ipv4, r->n_ipv4, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->ipv6, r->n_ipv6, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->inner, r->n_inner, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->nol4, r->n_nol4, __ATOMIC_RELAXED);
+    __atomic_add_fetch(&t->other, r->n_other, __ATOMIC_RELAXED);
 }
 
 int pb_xlat_refuses(const pb_sequence_t *seq, int seq_num)
@@ -306,6 +339,11 @@ static int gb_xlat(void *h, void *src, const pbgpu_xlat_opts *opts, void *dst)
     pbgpu_frames *f = (pbgpu_frames *)src;
     return pbgpu_xlat46((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
 }
+static int gb_verify_wire(void *h, void *frames, const pbgpu_wire_opts *opts, pbgpu_wire_result *res)
+{
+    pbgpu_frames *f = (pbgpu_frames *)frames;
+    return pbgpu_verify_wire((pbgpu_ctx *)h, f, 0, f->n_frames, opts, res, NULL);
+}
 static void gb_free(void *h, void *frames)
 {
     pbgpu_frames_free((pbgpu_ctx *)h, (pbgpu_frames *)frames);
@@ -318,7 +356,8 @@ static void gb_close(void *h)
 static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, gb_n_frames, gb_land,
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
                                          gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment,
-                                         gb_stamp, gb_alloc_encap, gb_xlat}; /* a translation's buffer is sized as an encapsulation's */
+                                         gb_stamp, gb_alloc_encap, gb_xlat, /* a translation's buffer is sized as an encapsulation's */
+                                         gb_verify_wire};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -534,6 +573,24 @@ void pb_verify_failed_msg(int seq_num, uint64_t bad, uint64_t first_bad, uint64_
             "[%d] Verify failed for sequence #%d: %llu bad frame(s), the first at frame %llu of the batch "
             "starting at iteration %llu. Stopping the sequence.\n",
             seq_num, seq_num, (unsigned long long)bad, (unsigned long long)first_bad, (unsigned long long)first_iter);
+}
+
+void pb_verify_wire_failed_msg(int seq_num, uint64_t bad, uint64_t first_bad, uint64_t first_iter)
+{
+    fprintf(stderr,
+            "[%d] Verify failed for sequence #%d as sent: %llu bad frame(s), the first at frame %llu of the batch "
+            "starting at iteration %llu. Stopping the sequence.\n",
+            seq_num, seq_num, (unsigned long long)bad, (unsigned long long)first_bad, (unsigned long long)first_iter);
+}
+
+void pb_print_verified_wire(const pb_wire_tally_t *t)
+{
+    fprintf(stdout,
+            "Verified %llu frames as sent on the GPU: %llu bad (%llu IPv4, %llu IPv6, %llu with an inner frame, %llu "
+            "without an L4 checksum to check, %llu not IP).\n",
+            (unsigned long long)t->frames, (unsigned long long)t->bad, (unsigned long long)t->ipv4,
+            (unsigned long long)t->ipv6, (unsigned long long)t->inner, (unsigned long long)t->nol4,
+            (unsigned long long)t->other);
 }
 
 void pb_print_sequence_total(int seq_num, uint64_t p, uint64_t b, time_t secs)
@@ -824,6 +881,10 @@ static void *gpu_worker(void *p)
         last_error = PBGPU_ENOTSUP;
         goto out;
     }
+    /* --verifywire: what this sequence's frames are asked, whatever shape they leave in */
+    const int vwire = vwire_on;
+    pbgpu_wire_opts wopts;
+    pb_wire_opts_for(seq, &wopts);
     /* --stamp: the batch's global frame index and the scheduled time of index 0 */
     const int stp = stamp_on;
     pbgpu_stamp_opts sopts = stamp_opts;
@@ -933,6 +994,27 @@ static void *gpu_worker(void *p)
             }
         }
         void *const lf = enc ? efr[cur] : bf; /* what lands: its lengths are what the ring and the totals count */
+        /* --verifywire: the batch as it leaves, after the last repack */
+        if (vwire)
+        {
+            pbgpu_wire_result wr;
+            if ((rc = B->verify_wire(ctx, lf, &wopts, &wr)) != 0)
+            {
+                fprintf(stderr, "[%d] Error verifying frames as sent on GPU %d :: %s.\n", seq_num, w->gpu,
+                        pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+            pb_wire_tally_add(&vwire_tally[w->seq_idx], &wr);
+            if (wr.n_bad)
+            {
+                pb_verify_wire_failed_msg(seq_num, wr.n_bad, wr.first_bad,
+                                          (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch);
+                last_error = PBGPU_EIO;
+                verify_failed[w->seq_idx] = 1;
+                break;
+            }
+        }
         /* double buffering: the next batch builds on the GPU while this one lands */
         const uint64_t n_next = claim_iters(w->seq_idx, seq->max_pckts, batch, fpi);
         if (n_next &&
@@ -1250,6 +1332,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
         last_error = PBGPU_ENOTSUP;
         return;
     }
+    if (vwire_on && builder->verify_wire == NULL)
+    {
+        fprintf(stderr, "[%d] --verifywire: this frame builder cannot verify frames as sent.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
+    }
     if (cmd.umem_slot && (cmd.umem_slot < 64 || cmd.umem_slot > PB_FRAME_SIZE || (cmd.umem_slot & (cmd.umem_slot - 1)) ||
                           (uint64_t)(cmd.umem_frames ? cmd.umem_frames : PB_NUM_FRAMES) * (PB_FRAME_SIZE / cmd.umem_slot) >
                               (1u << 22)))
@@ -1262,6 +1350,7 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     const uint16_t idx = seq_cnt++;
     start_time[idx] = time(NULL);
     verify_on[idx] = cmd.verify ? 1 : 0;
+    vwire_seq[idx] = vwire_on ? 1 : 0;
     stamp_t0[idx] = stamp_opts.t0_ns;
     if (stamp_on && !stamp_t0_set)
     {
@@ -1390,6 +1479,10 @@ int pb_shutdown_stats(pb_config_t *cfg)
     for (int i = 0; i < seq_cnt; ++i)
         if (verify_on[i])
             pb_print_verified(verified_frames[i], verified_bad[i]);
+    /* --verifywire: and one for the frames as they left */
+    for (int i = 0; i < seq_cnt; ++i)
+        if (vwire_seq[i])
+            pb_print_verified_wire(&vwire_tally[i]);
     fflush(stdout);
     return last_error;
 }
@@ -1422,6 +1515,8 @@ void pb_reset(void)
     memset(verified_frames, 0, sizeof verified_frames);
     memset(verified_bad, 0, sizeof verified_bad);
     memset(verify_on, 0, sizeof verify_on);
+    memset(vwire_seq, 0, sizeof vwire_seq);
+    memset(vwire_tally, 0, sizeof vwire_tally);
     memset((void *)verify_failed, 0, sizeof verify_failed);
     stop_requested = 0;
 }

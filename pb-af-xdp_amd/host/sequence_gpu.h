@@ -73,6 +73,24 @@ const pbgpu_xlat_opts *pb_get_xlat(void);
  * frame is not one the fragmenter splits), a UDP sequence without an L4 checksum (its zero
  * checksum would leave wrong: IPv6 has no "none").  0: the sequence can be translated. */
 int pb_xlat_refuses(const pb_sequence_t *seq, int seq_num);
+/* --verifywire (main_gpu.c's own option): every batch is checked on the GPU as it leaves
+ * (pbgpu_verify_wire) - the buffer that lands or is packed, after the last repack, whatever --stamp,
+ * --fragment, --xlat6 and --encap made of it - once per batch and independent of --verify.  A bad frame
+ * stops the sequence as --verify's does.  0: off (the default). */
+void pb_set_verify_wire(int on);
+int pb_get_verify_wire(void);
+/* What --verifywire asks of a sequence's frames: L3_CSUM | L3_LEN with ip.csum (L3_LEN always under
+ * --xlat6, whose header has nothing else), L4_CSUM with l4_csum, UDP_LEN always; a VXLAN inner frame
+ * is looked for behind --encap vxlan's destination port. */
+void pb_wire_opts_for(const pb_sequence_t *seq, pbgpu_wire_opts *opts);
+/* a sequence's --verifywire totals and its end-of-run line */
+typedef struct pb_wire_tally
+{
+    uint64_t frames, bad, ipv4, ipv6, inner, nol4, other;
+} pb_wire_tally_t;
+void pb_wire_tally_add(pb_wire_tally_t *t, const pbgpu_wire_result *r);
+void pb_print_verified_wire(const pb_wire_tally_t *t);
+void pb_verify_wire_failed_msg(int seq_num, uint64_t bad, uint64_t first_bad, uint64_t first_iter);
 
 void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cmd_line_af_xdp cmd);
 /* sequence.c:779-824: stop and join the workers, print the end-of-run lines,
@@ -144,6 +162,9 @@ typedef struct pb_builder
      * one.  NULL: --xlat6 is refused. */
     int (*alloc_xlat)(void *h, uint16_t seq_idx, uint64_t n_iter, uint32_t extra, void **frames, uint32_t *max_len);
     int (*xlat)(void *h, void *src, const pbgpu_xlat_opts *opts, void *dst);
+    /* --verifywire: the batch in `frames` checked as it leaves (pbgpu_verify_wire over all of its
+     * frames).  NULL: --verifywire is refused. */
+    int (*verify_wire)(void *h, void *frames, const pbgpu_wire_opts *opts, pbgpu_wire_result *res);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

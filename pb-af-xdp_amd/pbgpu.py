@@ -318,6 +318,49 @@ class XlatResult(C.Structure):
     ]
 
 
+WIRE_L3_CSUM = 1  # every IPv4 header parsed folds to 0xFFFF
+WIRE_L3_LEN = 2  # IPv4 tot_len / IPv6 payload length agree with the frame's length
+WIRE_L4_CSUM = 4  # UDP / TCP / ICMP / ICMPv6 checksum
+WIRE_UDP_LEN = 8  # a UDP header's length field
+WIRE_ALL = 15
+WIRE_MALFORMED = 16  # code bit only, always checked
+WIRE_NOL4 = 32  # info bit: IP, but no L4 checksum that can be evaluated
+WIRE_INNER = 64  # info bit: a VXLAN inner frame was parsed
+WIRE_OTHER = 128  # info bit: not IP, nothing checked
+
+
+class WireOpts(C.Structure):
+    """pbgpu_wire_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("checks", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("vxlan_port", C.c_uint16),
+        ("reserved", C.c_uint16 * 3),
+    ]
+
+
+class WireResult(C.Structure):
+    """pbgpu_wire_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_checked", C.c_uint64),
+        ("n_bad", C.c_uint64),
+        ("bad_malformed", C.c_uint64),
+        ("bad_l3_csum", C.c_uint64),
+        ("bad_l3_len", C.c_uint64),
+        ("bad_l4_csum", C.c_uint64),
+        ("bad_udp_len", C.c_uint64),
+        ("first_bad", C.c_uint64),
+        ("n_ipv4", C.c_uint64),
+        ("n_ipv6", C.c_uint64),
+        ("n_inner", C.c_uint64),
+        ("n_nol4", C.c_uint64),
+        ("n_other", C.c_uint64),
+        ("device_ms", C.c_double),
+    ]
+
+
 # ------------------------------------------------------------- sequences
 def _b(s: Optional[str]) -> Optional[bytes]:
     return None if s is None else s.encode()
@@ -482,6 +525,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_stamp": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(StampOpts), C.POINTER(StampResult)]),
         "pbgpu_xlat46_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), U64P, U64P]),
         "pbgpu_xlat46": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), FP, C.POINTER(XlatResult)]),
+        "pbgpu_verify_wire": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(WireOpts), C.POINTER(WireResult), P]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
     }
@@ -561,6 +605,21 @@ class FrameBuffer:
         out = np.zeros(n if codes else 0, dtype=np.uint8)
         _check(self.ctx.lib.pbgpu_verify(self.ctx.h, self.ptr, first, n, checks, C.byref(res),
                                          out.ctypes.data if codes and n else None), "verify")
+        return (res, out) if codes else res
+
+    def verify_wire(self, first: int = 0, n: Optional[int] = None, checks: int = WIRE_ALL, vxlan_port: int = 0,
+                    codes: bool = False):
+        """Checks frames [first, first + n) on the GPU as they would leave (n None: to the last frame):
+        VLAN tags, IPv4 with options or IPv6, and behind UDP port vxlan_port a VXLAN inner frame are
+        parsed from the frame's own bytes.  Returns the WireResult, and with codes=True also each
+        frame's code (np.uint8, WIRE_* bits)."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        opts = WireOpts(checks, 0, vxlan_port)
+        res = WireResult()
+        out = np.zeros(n if codes else 0, dtype=np.uint8)
+        _check(self.ctx.lib.pbgpu_verify_wire(self.ctx.h, self.ptr, first, n, C.byref(opts), C.byref(res),
+                                              out.ctypes.data if codes and n else None), "verify_wire")
         return (res, out) if codes else res
 
     def upload(self, data, offsets=None, fixed_len: int = 0) -> None:
