@@ -532,6 +532,62 @@ typedef struct pbgpu_wire_result {
 int pbgpu_verify_wire(pbgpu_ctx *ctx, pbgpu_frames *frames, uint64_t first_frame, uint64_t n,
                       const pbgpu_wire_opts *opts, pbgpu_wire_result *res, uint8_t *codes_out);
 
+/* ---- L4 segmentation: built (or uploaded) TCP and UDP frames cut into MSS-sized segments, each
+ * with headers and checksums of its own (TSO / UDP_SEGMENT), on the device ---- */
+#define PBGPU_SEG_NO_L4_CSUM 1u  /* the L4 checksum field is copied from the source as it is; no payload byte is summed */
+#define PBGPU_SEG_FIXED_ID   2u  /* every segment keeps the source's IPv4 ID; else ID + i */
+typedef struct pbgpu_seg_opts {
+    uint32_t mss;      /* L4 payload bytes per segment, 8..65535; else -EINVAL */
+    uint32_t flags;    /* PBGPU_SEG_*; any other bit: -EINVAL */
+    uint64_t reserved; /* must be 0 */
+} pbgpu_seg_opts;
+typedef struct pbgpu_seg_result {
+    uint64_t n_in, n_out;      /* source frames taken, frames written */
+    uint64_t n_split_tcp;      /* TCP source frames written as 2 or more segments */
+    uint64_t n_split_udp;      /* UDP ones */
+    uint64_t n_other;          /* L - 42 > mss but not eligible (see below), copied whole */
+    uint64_t out_bytes;
+    uint32_t out_min_len, out_max_len;
+    double   device_ms;        /* all launches of the call, one event pair */
+} pbgpu_seg_result;
+
+/* A source frame F of length L is eligible when L >= 34, F[12:14] = 08 00, F[14] = 0x45,
+ * BE16(F[20:22]) & 0x3FFF = 0 (not a fragment) and it is UDP (F[23] = 17, L >= 42, H = 8) or TCP
+ * (F[23] = 6, L >= 54, H = 4 (F[46] >> 4), 20 <= H, 34 + H <= L; options allowed).  The frame length
+ * decides, never a stored length.  P = L - 34 - H.  A frame that is not eligible or has P <= mss is
+ * copied as one output frame, unchanged; n_other counts the ineligible ones with L - 42 > mss (a
+ * frame with L - 42 <= mss cannot split and is not read).  Otherwise it becomes K = ceil(P / mss)
+ * frames; segment i carries Pi = min(mss, P - i mss) payload bytes F[34+H+i mss : 34+H+i mss+Pi]
+ * behind F[0:14], the 20 IPv4 header bytes with tot_len = 20 + H + Pi, ID = (ID + i) mod 2^16
+ * (unchanged under FIXED_ID) and the header checksum recomputed (RFC 1071), all else kept, and
+ *   TCP: the H header bytes with the sequence number + i mss (mod 2^32), FIN and PSH cleared in every
+ *        segment but the last, CWR cleared in every segment but the first, options copied, and the
+ *        checksum over the pseudo header (addresses, 6, H + Pi) and the segment, 0x0000 kept;
+ *   UDP: the ports, length 8 + Pi and the checksum over the pseudo header (17, 8 + Pi) and the
+ *        datagram, 0x0000 stored as 0xFFFF (RFC 768).
+ * Under NO_L4_CSUM the two checksum bytes are the source's in every segment.
+ * pbgpu_segment writes the output frames packed from byte 0 of dst->data in source and segment order,
+ * zeros up to the next multiple of 16 and nothing past that.  dst is then a frames buffer as after
+ * an upload: n_frames = n_out, fixed_len = 0 with the device offsets[0 .. n_out] written (fixed_len =
+ * src->fixed_len for a fixed-length source with src->fixed_len - 42 <= mss: a plain copy, no count
+ * pass), total_bytes, and the exact shortest and longest output frame recorded.  src is only read;
+ * pbgpu_counters is unchanged; no environment variable is read.  Ordering on the context's stream,
+ * n == 0 and "dst unchanged on any error" as pbgpu_fragment.
+ * pbgpu_segment_size gives the exact output frame count and bytes (the count and scan passes only).
+ * pbgpu_segment_bound answers from src's recorded longest frame with no device work: with Kmax =
+ * max(1, ceil((max_len - 42) / mss)), frames <= n Kmax and bytes <= n max_len + 94 n (Kmax - 1) for a
+ * variable-length source (the range's exact bytes + 94 n (Kmax - 1) for a fixed-length one).
+ * -EINVAL: NULL arguments, src never built or uploaded, a range past src->n_frames, src == dst or
+ * overlapping data, mss outside 8..65535, unknown flag bits, reserved != 0, src's shortest frame
+ * below 14 B (and a range that ends past byte 2^44 of src->data).  -ENOSPC: dst->capacity_frames <
+ * n_out or dst->capacity_bytes below the output rounded up to 16. */
+int pbgpu_segment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                       const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_segment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                        const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes);
+int pbgpu_segment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                  const pbgpu_seg_opts *opts, pbgpu_frames *dst, pbgpu_seg_result *res /* may be NULL */);
+
 /* ---- counters (sequence.c:12-14, 633-642): frames built / bytes stored per
  * sequence since open, recorded by the build kernels' workgroups as they finish
  * their share (a skipped or short build shows here) and folded into the totals
@@ -588,7 +644,8 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
  *        10 sizeof(pbgpu_frag_opts), 11 sizeof(pbgpu_frag_result),
  *        12 sizeof(pbgpu_stamp_opts), 13 sizeof(pbgpu_stamp_result),
  *        14 sizeof(pbgpu_xlat_opts), 15 sizeof(pbgpu_xlat_result),
- *        16 sizeof(pbgpu_wire_opts), 17 sizeof(pbgpu_wire_result);
+ *        16 sizeof(pbgpu_wire_opts), 17 sizeof(pbgpu_wire_result),
+ *        18 sizeof(pbgpu_seg_opts), 19 sizeof(pbgpu_seg_result);
  * returns 0 for an unknown index. */
 size_t pbgpu_abi_size(int which);
 

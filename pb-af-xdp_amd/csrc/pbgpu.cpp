@@ -53,6 +53,7 @@ extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t 
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_seg(const pb_sgargs *A, int stage, int G, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st);
 extern "C" hipError_t pbk_launch_xlat(const pb_xlargs *A, int stage, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
@@ -310,6 +311,14 @@ struct pbgpu_ctx
     uint64_t fg_cnt_cap = 0; // source frames
     uint64_t *d_fg_map = nullptr;
     uint64_t fg_map_cap = 0; // output records
+    // pbgpu_segment: the count pass's scratch (result words, two row sums, K and H per source frame),
+    // the map entries and the slice sums of the output records
+    uint8_t *d_sg_cnt = nullptr;
+    uint64_t sg_cnt_cap = 0; // source frames
+    uint64_t *d_sg_map = nullptr;
+    uint64_t sg_map_cap = 0; // output records
+    uint32_t *d_sg_psum = nullptr;
+    uint64_t sg_psum_cap = 0; // output records
     unsigned long long *d_sp_res = nullptr; // pbgpu_stamp: the result words
     unsigned long long *d_xl_res = nullptr; // pbgpu_xlat46: the classify pass's result words
     seq_slot seqs[PB_MAX_SEQUENCES];
@@ -839,6 +848,12 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipFree(ctx->d_fg_cnt);
     if (ctx->d_fg_map)
         (void)hipFree(ctx->d_fg_map);
+    if (ctx->d_sg_cnt)
+        (void)hipFree(ctx->d_sg_cnt);
+    if (ctx->d_sg_map)
+        (void)hipFree(ctx->d_sg_map);
+    if (ctx->d_sg_psum)
+        (void)hipFree(ctx->d_sg_psum);
     if (ctx->d_sp_res)
         (void)hipFree(ctx->d_sp_res);
     if (ctx->d_xl_res)
@@ -3088,6 +3103,204 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
     return mark_built(ctx, dst, st);
 }
 
+// ---- L4 segmentation ----
+
+// Argument checks shared by the three calls; nothing on the device.
+static int seg_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_seg_opts *opts)
+{
+    if (ctx == NULL || src == NULL || opts == NULL)
+        return PBGPU_EINVAL;
+    if (opts->mss < 8u || opts->mss > 65535u || (opts->flags & ~(PBGPU_SEG_NO_L4_CSUM | PBGPU_SEG_FIXED_ID)) ||
+        opts->reserved != 0)
+        return PBGPU_EINVAL;
+    if (!frames_range_ok(src, first, n))
+        return PBGPU_EINVAL;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (src->n_frames && fs->min_len < 14u)
+        return PBGPU_EINVAL;
+    return PBGPU_OK;
+}
+
+static void seg_args(pb_sgargs *A, const pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_seg_opts *opts)
+{
+    memset(A, 0, sizeof *A);
+    A->src = src->data;
+    A->offsets = src->fixed_len ? nullptr : src->offsets;
+    A->first = first;
+    A->n = n;
+    A->fixed_len = src->fixed_len;
+    A->mss = opts->mss;
+    A->mdiv = make_div(opts->mss);
+    A->flags = ((opts->flags & PBGPU_SEG_NO_L4_CSUM) ? PB_SG_NO_L4 : 0u) |
+               ((opts->flags & PBGPU_SEG_FIXED_ID) ? PB_SG_FIXED_ID : 0u);
+}
+
+// The count and the two scans, queued on the context's stream: A's scratch pointers are set, the
+// result words arrive in res[] with the stream's next synchronise.
+static int seg_count(pbgpu_ctx *ctx, pb_sgargs *A, unsigned long long *res)
+{
+    const uint64_t nblk = (A->n + PB_FG_WT - 1u) / PB_FG_WT;
+    if (nblk > 0xFFFFFFFFull)
+        return PBGPU_EINVAL;
+    PBCHK(scratch_reserve((void **)&ctx->d_sg_cnt, &ctx->sg_cnt_cap, A->n, PB_SG_RES_DW * 8u + nblk * 16u + A->n * 4u));
+    A->res = (unsigned long long *)ctx->d_sg_cnt;
+    A->bsum = A->res + PB_SG_RES_DW;
+    A->xsum = A->bsum + nblk;
+    A->kcnt = (uint32_t *)(A->xsum + nblk);
+    HIPCHK(pbk_launch_seg(A, 0, 0, 0, ctx->stream));
+    HIPCHK(hipMemcpyAsync(res, A->res, PB_SG_RES_DW * 8u, hipMemcpyDeviceToHost, ctx->stream));
+    return PBGPU_OK;
+}
+
+int pbgpu_segment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                        const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    PBCHK(seg_check(ctx, src, first_frame, n, opts));
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const uint64_t mss = opts->mss, max_len = fs->max_len;
+    uint64_t kmax = 1;
+    if (max_len > mss + 42ull)
+        kmax = (max_len - 42u + mss - 1u) / mss;
+    *frames = n * kmax;
+    *bytes = n * (src->fixed_len ? src->fixed_len : max_len) + 94u * n * (kmax - 1u);
+    return PBGPU_OK;
+}
+
+int pbgpu_segment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
+                       const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    PBCHK(seg_check(ctx, src, first_frame, n, opts));
+    uint64_t body = 0, src_end = 0;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
+    *frames = n;
+    *bytes = body;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (n == 0 || fs->max_len <= opts->mss + 42u) // nothing can split
+        return PBGPU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    pb_sgargs A;
+    seg_args(&A, src, first_frame, n, opts);
+    unsigned long long r[PB_SG_RES_DW];
+    PBCHK(seg_count(ctx, &A, r));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (r[0] < n)
+        return PBGPU_EIO;
+    *frames = r[0];
+    *bytes = body + r[6];
+    return PBGPU_OK;
+}
+
+int pbgpu_segment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_seg_opts *opts,
+                  pbgpu_frames *dst, pbgpu_seg_result *res)
+{
+    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
+        return PBGPU_EINVAL;
+    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+        return PBGPU_EINVAL;
+    PBCHK(seg_check(ctx, src, first_frame, n, opts));
+    uint64_t body = 0, src_end = 0;
+    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    hipStream_t st = ctx->stream;
+    // a fixed-length source none of whose frames can split: no count, a plain copy
+    const bool copy = src->fixed_len && src->fixed_len <= opts->mss + 42u;
+    pb_sgargs A;
+    seg_args(&A, src, first_frame, n, opts);
+    unsigned long long r[PB_SG_RES_DW] = {n, 0, 0, 0, src->fixed_len, src->fixed_len, 0, 0};
+    timing_pair tp = {nullptr, nullptr};
+    if (n)
+    {
+        PBCHK(timed_begin(ctx, &tp)); // the timed stretch: count, scans, map, sums and writer
+        if (!copy)
+        {
+            // the count and scans run, and their result is read, before anything of dst is touched
+            PBCHK(seg_count(ctx, &A, r));
+            HIPCHK(hipStreamSynchronize(st));
+            if (r[0] < n)
+                return PBGPU_EIO;
+        }
+    }
+    const uint64_t n_out = n ? r[0] : 0;
+    const uint64_t total = body + (n ? r[6] : 0);
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    const bool sums = !(opts->flags & PBGPU_SEG_NO_L4_CSUM);
+    if (n && !copy)
+    {
+        if (src_end >> PB_SG_M_ISH) // a map entry keeps 44 bits of source offset
+            return PBGPU_EINVAL;
+        PBCHK(scratch_reserve((void **)&ctx->d_sg_map, &ctx->sg_map_cap, n_out, n_out * sizeof(uint64_t)));
+        if (sums)
+            PBCHK(scratch_reserve((void **)&ctx->d_sg_psum, &ctx->sg_psum_cap, n_out, n_out * sizeof(uint32_t)));
+    }
+    frames_events *fe = nullptr;
+    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, &fe));
+    float ms = 0;
+    if (n)
+    {
+        uint32_t grid = 0, per = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, &per, &grid));
+        if (copy)
+        {
+            pb_fgargs F;
+            memset(&F, 0, sizeof F);
+            F.src = src->data;
+            F.dst = dst->data;
+            F.first = first_frame;
+            F.n = n;
+            F.fixed_len = src->fixed_len;
+            F.total = total;
+            F.end16 = end16;
+            F.per = per;
+            HIPCHK(pbk_launch_frag(&F, 2, grid, st));
+        }
+        else
+        {
+            A.dst = dst->data;
+            A.dst_offsets = dst->offsets;
+            A.map = ctx->d_sg_map;
+            A.psum = ctx->d_sg_psum;
+            A.n_out = n_out;
+            A.total = total;
+            A.end16 = end16;
+            A.per = per;
+            A.hdw = 10u + (uint32_t)(r[7] < 15u ? r[7] : 15u);
+            // lanes per segment by the slice length, as verify_shape picks pb_vst_kernel's G
+            const int G = !sums ? 0 : opts->mss <= 256u ? 8 : opts->mss <= 512u ? 16 : opts->mss <= 2048u ? 32 : 64;
+            HIPCHK(pbk_launch_seg(&A, 1, G, grid, st));
+        }
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &ms));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = n_out;
+    dst->fixed_len = (n && copy) ? src->fixed_len : 0;
+    dst->total_bytes = total;
+    if (res)
+    {
+        memset(res, 0, sizeof *res);
+        res->n_in = n;
+        res->n_out = n_out;
+        res->n_split_tcp = n ? r[1] : 0;
+        res->n_split_udp = n ? r[2] : 0;
+        res->n_other = n ? r[3] : 0;
+        res->out_bytes = total;
+        res->out_min_len = fe->min_len;
+        res->out_max_len = fe->max_len;
+        res->device_ms = ms;
+    }
+    return mark_built(ctx, dst, st);
+}
+
 // ---- stamping ----
 
 int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, const pbgpu_stamp_opts *opts,
@@ -3836,6 +4049,8 @@ size_t pbgpu_abi_size(int which)
     case 9: return sizeof(pbgpu_encap_opts);
     case 10: return sizeof(pbgpu_frag_opts);
     case 11: return sizeof(pbgpu_frag_result);
+    case 18: return sizeof(pbgpu_seg_opts);
+    case 19: return sizeof(pbgpu_seg_result);
     case 12: return sizeof(pbgpu_stamp_opts);
     case 13: return sizeof(pbgpu_stamp_result);
     case 14: return sizeof(pbgpu_xlat_opts);

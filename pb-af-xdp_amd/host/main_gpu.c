@@ -44,6 +44,9 @@ static int encap_twice;
 /* --fragment MTU[:ignoredf], once: handed to the driver with pb_set_fragment */
 static const char *fragment_spec;
 static int fragment_twice;
+/* --segment MSS[:fixedid], once: handed to the driver with pb_set_segment */
+static const char *segment_spec;
+static int segment_twice;
 /* --stamp head[:OFF] | tail[:OFF], once: handed to the driver with pb_set_stamp */
 static const char *stamp_spec;
 static int stamp_twice;
@@ -65,7 +68,7 @@ enum
     O_DMAC, O_MINTTL, O_MAXTTL, O_MINID, O_MAXID, O_SIP, O_DIP, O_PROTOCOL, O_TOS, O_L3CSUM, O_USPORT, O_UDPORT,
     O_TSPORT, O_TDPORT, O_SYN, O_ACK, O_PSH, O_RST, O_FIN, O_URG, O_ECE, O_CWR, O_PMIN, O_PMAX, O_PSTATIC, O_PEXACT,
     O_PFILE, O_PSTRING, O_TIME, O_SECOND_PASS, O_PCAPDUMP, O_PCAPT0, O_ENCAP, O_FRAGMENT, O_STAMP,
-    O_XLAT6, O_VERIFYWIRE,
+    O_XLAT6, O_VERIFYWIRE, O_SEGMENT,
 };
 
 static const struct option common_opts[] = {
@@ -107,7 +110,7 @@ static const struct option common_opts[] = {
     {"pcapdump", required_argument, NULL, O_PCAPDUMP}, {"pcapt0", required_argument, NULL, O_PCAPT0},
     {"encap", required_argument, NULL, O_ENCAP}, {"fragment", required_argument, NULL, O_FRAGMENT},
     {"stamp", required_argument, NULL, O_STAMP}, {"xlat6", required_argument, NULL, O_XLAT6},
-    {"verifywire", no_argument, NULL, O_VERIFYWIRE},
+    {"verifywire", no_argument, NULL, O_VERIFYWIRE}, {"segment", required_argument, NULL, O_SEGMENT},
     {NULL, 0, NULL, 0},
 };
 
@@ -213,6 +216,11 @@ static void parse_common(int argc, char **argv, cmd_line_t *cmd, pb_sequence_t *
             xlat_spec = a;
             break;
         case O_VERIFYWIRE: verify_wire = 1; break;
+        case O_SEGMENT:
+            if (segment_spec && segment_spec != a)
+                segment_twice = 1;
+            segment_spec = a;
+            break;
         default: break;
         }
     }
@@ -349,6 +357,39 @@ static int parse_fragment(const char *spec, pbgpu_frag_opts *o, const char **why
     return 0;
 }
 
+/* --segment's argument MSS[:fixedid] -> the options; -1 and a message in `why` for a malformed one */
+static int parse_segment(const char *spec, pbgpu_seg_opts *o, const char **why)
+{
+    char buf[32];
+    memset(o, 0, sizeof *o);
+    if (strlen(spec) >= sizeof buf)
+    {
+        *why = "too long";
+        return -1;
+    }
+    strcpy(buf, spec);
+    char *opt = strchr(buf, ':');
+    if (opt)
+        *opt++ = '\0';
+    uint32_t v = 0;
+    if (field_u32(buf, 65535, &v) != 0 || v < 8)
+    {
+        *why = "MSS is 8-65535";
+        return -1;
+    }
+    o->mss = v;
+    if (opt)
+    {
+        if (strcmp(opt, "fixedid") != 0)
+        {
+            *why = "expected MSS[:fixedid]";
+            return -1;
+        }
+        o->flags = PBGPU_SEG_FIXED_ID;
+    }
+    return 0;
+}
+
 /* --stamp's argument head[:OFF] | tail[:OFF] -> the offset and flags; -1 and a message in `why` for a
  * malformed one */
 static int parse_stamp(const char *spec, pbgpu_stamp_opts *o, const char **why)
@@ -460,7 +501,7 @@ static void print_cmd_help(void)
                     "AF_XDP: --queue --nowakeup --sharedumem --batchsize --skb --zerocopy --copy\n"
                     "GPU: --gpus N --gpu I --gpubatch K --seed S --veryrandom --literal --singlefold --pcap FILE --tx xsk "
                     "--umemframes N --umemslot S --verify --pcapdump FILE --pcapt0 NS --encap SPEC --fragment MTU[:ignoredf] "
-                    "--stamp head[:OFF]|tail[:OFF] --xlat6 SRC6/96[,DST6/96][:hashflow] --verifywire\n"
+                    "--stamp head[:OFF]|tail[:OFF] --xlat6 SRC6/96[,DST6/96][:hashflow] --verifywire --segment MSS[:fixedid]\n"
                     "--verify => Check every built batch's checksums and lengths on the GPU as it is built (and stamped): "
                     "Ethernet + IPv4 without options. Of a repacked batch it sees the IPv4 checksum and length of "
                     "fragments and of a VXLAN outer header, nothing of a VLAN or IPv6 frame.\n"
@@ -487,7 +528,13 @@ static void print_cmd_help(void)
                     "stateless) after it is stamped and verified and before it is encapsulated, sent or dumped: the IPv4 "
                     "addresses go behind the /96 prefixes (RFC 6052; one prefix serves both), TOS and TTL carry over, the "
                     "TCP / UDP / ICMP echo checksums are updated. :hashflow hashes the flow label from addresses and "
-                    "ports (default 0). Not with --fragment, nor with a UDP sequence whose l4csum is 0.\n");
+                    "ports (default 0). Not with --fragment, nor with a UDP sequence whose l4csum is 0.\n"
+                    "--segment MSS[:fixedid] => Cut every built TCP or UDP frame with more than MSS (8-65535) payload bytes "
+                    "into segments of MSS bytes on the GPU, as TSO and UDP_SEGMENT do: each with its own IPv4 length, ID "
+                    "(ID + i; :fixedid keeps the packet's) and checksum, its own TCP sequence number and flags or UDP "
+                    "length, and an L4 checksum of its own unless l4csum is 0. After --stamp and --verify, before the "
+                    "batch is verified again, fragmented, translated, encapsulated, sent or dumped. --maxpckts counts "
+                    "built packets, the byte limits what is sent.\n");
 }
 
 int main(int argc, char **argv)
@@ -549,6 +596,22 @@ int main(int argc, char **argv)
             return EXIT_FAILURE;
         }
         pb_set_fragment(&fo);
+    }
+    if (segment_spec)
+    {
+        pbgpu_seg_opts go;
+        const char *why = NULL;
+        if (segment_twice)
+        {
+            fprintf(stderr, "--segment given more than once: one MSS per run.\n");
+            return EXIT_FAILURE;
+        }
+        if (parse_segment(segment_spec, &go, &why) != 0)
+        {
+            fprintf(stderr, "--segment %s: %s.\n", segment_spec, why);
+            return EXIT_FAILURE;
+        }
+        pb_set_segment(&go);
     }
     if (stamp_spec)
     {

@@ -2,7 +2,8 @@
  * pcap_dump.c — pcktbatch-gpu --pcapdump (pcap_dump.h).
  *
  * Per sequence: two frame buffers and two stream buffers on the GPU, two registered host buffers.
- * Batch k is (with --stamp stamped in place, verified, with --fragment fragmented into a fragment buffer
+ * Batch k is (with --stamp stamped in place, verified, with --segment cut into segments in a buffer of
+ * their own and verified again, with --fragment fragmented into a fragment buffer
  * and verified again, with --xlat6 translated to IPv6 into a buffer of its own, with --encap encapsulated
  * into a third frame buffer,) packed into stream buffer k & 1; batch k + 1's build is queued into the
  * other frame buffer; then stream k is copied to its host buffer in one piece and written with
@@ -94,6 +95,7 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
     pbgpu_frames *enc = NULL; /* --encap: the batch as it is packed (the pack returns before the next encap) */
     pbgpu_frames *frg = NULL; /* --fragment: the batch's fragments (what is encapsulated, or packed) */
     pbgpu_frames *x6 = NULL;  /* --xlat6: the batch as IPv6 (what is encapsulated, or packed) */
+    pbgpu_frames *sgm = NULL; /* --segment: the batch's segments (what is fragmented, translated, encapsulated or packed) */
     uint8_t *hb[2] = {NULL, NULL};
     int reg[2] = {0, 0};
     int rc;
@@ -137,15 +139,36 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
      * the size bound is then the frames times that frame, plus 16) */
     const pbgpu_frag_opts *fo = pb_get_fragment();
     uint64_t of = mf, obytes = mb; /* the frames and bytes a batch can become before it is encapsulated */
-    if (fo)
+    /* --segment: first, so the fragmenter's bound below starts from the segments (94 bytes of headers
+     * at the most for each but a frame's first) */
+    const int segm = pb_get_segment() != NULL;
+    pbgpu_seg_opts sgo;
+    memset(&sgo, 0, sizeof sgo);
+    uint64_t longest = 0;
+    if (segm || fo)
     {
         uint64_t f16 = 0, b16 = 0;
         if ((rc = pbgpu_build_size(ctx, idx, 16, &f16, &b16)) != 0)
             goto out;
-        const uint64_t longest = f16 ? (b16 - 16) / f16 : 0, c = (fo->mtu - 20u) & ~7u;
+        longest = f16 ? (b16 - 16) / f16 : 0;
+    }
+    if (segm)
+    {
+        sgo = *pb_get_segment();
+        uint32_t ks = 1, piece = 0;
+        pb_seg_plan_for(seq, &sgo, (uint32_t)longest, &ks, &piece);
+        of = mf * ks;
+        obytes = mb + 94 * mf * (ks - 1) + 16;
+        longest = piece;
+        if ((rc = pbgpu_frames_alloc(ctx, of, obytes, &sgm)) != 0)
+            goto out;
+    }
+    if (fo)
+    {
+        const uint64_t c = (fo->mtu - 20u) & ~7u;
         const uint64_t kmax = longest > fo->mtu + 14ull ? (longest - 34 + c - 1) / c : 1;
-        of = mf * kmax;
-        obytes = mb + 34 * mf * (kmax - 1) + 16;
+        obytes += 34 * of * (kmax - 1) + 16;
+        of *= kmax;
         if ((rc = pbgpu_frames_alloc(ctx, of, obytes, &frg)) != 0)
             goto out;
     }
@@ -219,9 +242,37 @@ static int dump_sequence(dump_state_t *D, const pb_sequence_t *seq, uint16_t idx
         const uint64_t take = have < quota - done ? have : quota - done; /* the last batch: up to the quota */
         pbgpu_frames *bf = src[cur]; /* the batch as it is encapsulated or packed, and its frames */
         uint64_t btake = take;
+        if (segm)
+        {
+            if ((rc = pbgpu_segment(ctx, src[cur], 0, take, &sgo, sgm, NULL)) != 0)
+            {
+                fprintf(stderr, "[%d] Error segmenting frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                        pbgpu_strerror(rc));
+                goto out;
+            }
+            bf = sgm;
+            btake = sgm->n_frames;
+            if (D->cmd->verify) /* segments are plain frames the verifier parses: the sequence's own checks again */
+            {
+                pbgpu_verify_result r;
+                if ((rc = pbgpu_verify(ctx, sgm, 0, btake, vchecks, &r, NULL)) != 0)
+                {
+                    fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
+                            pbgpu_strerror(rc));
+                    goto out;
+                }
+                if (r.n_bad)
+                {
+                    *n_bad += r.n_bad;
+                    pb_verify_failed_msg(seq_num, r.n_bad, r.first_bad, iter);
+                    rc = PBGPU_EIO;
+                    goto out;
+                }
+            }
+        }
         if (fo)
         {
-            if ((rc = pbgpu_fragment(ctx, src[cur], 0, take, fo, frg, NULL)) != 0)
+            if ((rc = pbgpu_fragment(ctx, bf, 0, btake, fo, frg, NULL)) != 0)
             {
                 fprintf(stderr, "[%d] Error fragmenting frames on GPU %d :: %s.\n", seq_num, D->cmd->gpu_first,
                         pbgpu_strerror(rc));
@@ -342,6 +393,7 @@ out:
     pbgpu_frames_free(ctx, enc);
     pbgpu_frames_free(ctx, frg);
     pbgpu_frames_free(ctx, x6);
+    pbgpu_frames_free(ctx, sgm);
     *n_done = done;
     *n_packed = packed;
     *b_packed = packed_b;
@@ -432,9 +484,11 @@ int pb_pcap_dump(const pb_config_t *cfg, int seq_cnt, const struct cmd_line_af_x
     {
         /* --fragment: the packets are the built ones (the quota's), the bytes what the file holds, and
          * the frames packed follow on a line of their own */
-        pb_print_sequence_total(i + 1, p[i], pb_get_fragment() ? packed_b[i] : b[i], secs[i]);
+        pb_print_sequence_total(i + 1, p[i], pb_get_fragment() || pb_get_segment() ? packed_b[i] : b[i], secs[i]);
         if (pb_get_fragment())
             fprintf(stdout, "[%d] Fragmented into %llu frames.\n", i + 1, (unsigned long long)packed[i]);
+        else if (pb_get_segment()) /* --segment likewise: built packets, the file's bytes, the frames packed */
+            fprintf(stdout, "[%d] Segmented into %llu frames.\n", i + 1, (unsigned long long)packed[i]);
     }
     for (int i = 0; i < ran && cmd->verify; ++i)
         pb_print_verified(verified[i], bad[i]);

@@ -64,6 +64,8 @@ static int encap_on; /* --encap (pb_set_encap) */
 static pbgpu_encap_opts encap_opts;
 static int frag_on; /* --fragment (pb_set_fragment) */
 static pbgpu_frag_opts frag_opts;
+static int seg_on; /* --segment (pb_set_segment) */
+static pbgpu_seg_opts seg_opts;
 static int stamp_on; /* --stamp (pb_set_stamp) */
 static int stamp_t0_set;
 static pbgpu_stamp_opts stamp_opts;
@@ -117,6 +119,36 @@ void pb_set_fragment(const pbgpu_frag_opts *opts)
 const pbgpu_frag_opts *pb_get_fragment(void)
 {
     return frag_on ? &frag_opts : NULL;
+}
+
+void pb_set_segment(const pbgpu_seg_opts *opts)
+{
+    seg_on = opts != NULL;
+    if (opts)
+        seg_opts = *opts;
+}
+
+const pbgpu_seg_opts *pb_get_segment(void)
+{
+    return seg_on ? &seg_opts : NULL;
+}
+
+void pb_seg_plan_for(const pb_sequence_t *seq, pbgpu_seg_opts *opts, uint32_t longest, uint32_t *per_frame,
+                     uint32_t *piece)
+{
+    if (!seq->l4_csum)
+        opts->flags |= PBGPU_SEG_NO_L4_CSUM;
+    /* a built TCP header has no options; no protocol named is UDP */
+    const uint32_t hl = seq->ip.protocol == NULL || strcasecmp(seq->ip.protocol, "udp") == 0 ? 42u
+                        : strcasecmp(seq->ip.protocol, "tcp") == 0                            ? 54u
+                                                                                              : 0u;
+    *per_frame = 1;
+    *piece = longest;
+    if (hl && longest > hl + opts->mss)
+    {
+        *per_frame = (longest - hl + opts->mss - 1u) / opts->mss;
+        *piece = hl + opts->mss;
+    }
 }
 
 void pb_set_stamp(const pbgpu_stamp_opts *opts, int t0_set)
@@ -329,6 +361,19 @@ static int gb_fragment(void *h, void *src, const pbgpu_frag_opts *opts, void *ds
     pbgpu_frames *f = (pbgpu_frames *)src;
     return pbgpu_fragment((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
 }
+static int gb_alloc_seg(void *h, uint16_t i, uint64_t n_iter, uint32_t per_frame, uint32_t extra, void **frames)
+{
+    uint64_t mf = 0, mb = 0;
+    int rc = pbgpu_build_size((pbgpu_ctx *)h, i, n_iter, &mf, &mb);
+    if (rc == 0)
+        rc = pbgpu_frames_alloc((pbgpu_ctx *)h, mf * per_frame, mb + mf * extra + 16, (pbgpu_frames **)frames);
+    return rc;
+}
+static int gb_segment(void *h, void *src, const pbgpu_seg_opts *opts, void *dst)
+{
+    pbgpu_frames *f = (pbgpu_frames *)src;
+    return pbgpu_segment((pbgpu_ctx *)h, f, 0, f->n_frames, opts, (pbgpu_frames *)dst, NULL);
+}
 static int gb_stamp(void *h, void *frames, const pbgpu_stamp_opts *opts)
 {
     pbgpu_frames *f = (pbgpu_frames *)frames;
@@ -357,7 +402,7 @@ static const pb_builder_t gpu_builder = {gb_open, gb_load,  gb_alloc, gb_build, 
                                          gb_land_wait, gb_reg, gb_unreg, gb_free, gb_close, pbgpu_device_count,
                                          gb_verify, gb_alloc_encap, gb_encap, gb_alloc_frag, gb_fragment,
                                          gb_stamp, gb_alloc_encap, gb_xlat, /* a translation's buffer is sized as an encapsulation's */
-                                         gb_verify_wire};
+                                         gb_verify_wire, gb_alloc_seg, gb_segment};
 static const pb_builder_t *builder = &gpu_builder;
 
 void pb_set_builder(const pb_builder_t *b)
@@ -620,6 +665,7 @@ static void *gpu_worker(void *p)
     void *efr[2] = {NULL, NULL}; /* --encap: what is landed */
     void *ffr[2] = {NULL, NULL}; /* --fragment: the batch's fragments (what is encapsulated, or landed) */
     void *xfr[2] = {NULL, NULL}; /* --xlat6: the batch as IPv6 (what is encapsulated, or landed) */
+    void *sfr[2] = {NULL, NULL}; /* --segment: the batch's segments (what is fragmented, translated, encapsulated or landed) */
     uint8_t *umem = NULL;
     int registered = 0;
     pb_xsk_t xsk;
@@ -677,8 +723,22 @@ static void *gpu_worker(void *p)
      * bytes each), so a batch of them still fits the byte bound */
     const int frg = frag_on;
     const pbgpu_frag_opts fopts = frag_opts;
+    /* --segment: a frame's segments carry their headers (94 bytes at the most) each but the first; what
+     * follows it takes the segments as its frames */
+    const int sg = seg_on;
+    pbgpu_seg_opts sgopts = seg_opts;
+    uint32_t sg_k = 1, sg_piece = max_flen; /* segments a built frame can become, and the longest frame then */
+    if (sg)
+        pb_seg_plan_for(seq, &sgopts, max_flen, &sg_k, &sg_piece);
+    uint32_t sg_kf = 1; /* fragments a segment can become */
+    if (sg && frg && sg_piece > fopts.mtu + 14u)
+        sg_kf = (sg_piece - 34u + ((fopts.mtu - 20u) & ~7u) - 1u) / ((fopts.mtu - 20u) & ~7u);
+    /* bytes a batch's frame gains in all: the segments' headers, the fragments', then per frame that leaves */
+    const uint32_t sg_grow = (sg_k - 1u) * 94u, sg_fgrow = sg_grow + sg_k * (sg_kf - 1u) * 34u;
     uint64_t batch_flen = max_flen + enc_extra; /* bytes a built frame can become */
-    if (frg && max_flen > fopts.mtu + 14u)
+    if (sg)
+        batch_flen = max_flen + (uint64_t)sg_fgrow + (uint64_t)sg_k * sg_kf * (enc_extra + xl_extra);
+    else if (frg && max_flen > fopts.mtu + 14u)
     {
         const uint32_t c = (fopts.mtu - 20u) & ~7u, kmax = (max_flen - 34u + c - 1u) / c;
         batch_flen = max_flen + (uint64_t)(kmax - 1u) * 34u + (uint64_t)kmax * enc_extra;
@@ -724,7 +784,26 @@ static void *gpu_worker(void *p)
         last_error = rc;
         goto out;
     }
-    if (frg)
+    if (sg)
+    {
+        /* every buffer behind the segmenter is sized from the segments; whether they fit the UMEM
+         * slots is the landing's to say, from the lengths the buffer records */
+        if ((rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k, sg_grow, &sfr[0])) != 0 ||
+            (rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k, sg_grow, &sfr[1])) != 0 ||
+            (frg && ((rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k * sg_kf, sg_fgrow, &ffr[0])) != 0 ||
+                     (rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k * sg_kf, sg_fgrow, &ffr[1])) != 0)) ||
+            (xl && ((rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k, sg_grow + sg_k * xl_extra, &xfr[0])) != 0 ||
+                    (rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k, sg_grow + sg_k * xl_extra, &xfr[1])) != 0)) ||
+            (enc && ((rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k * sg_kf,
+                                        sg_fgrow + sg_k * sg_kf * (enc_extra + xl_extra), &efr[0])) != 0 ||
+                     (rc = B->alloc_seg(ctx, w->seq_idx, batch, sg_k * sg_kf,
+                                        sg_fgrow + sg_k * sg_kf * (enc_extra + xl_extra), &efr[1])) != 0)))
+        {
+            last_error = rc;
+            goto out;
+        }
+    }
+    if (frg && !sg)
     {
         uint32_t longest = 0;
         if ((rc = B->alloc_frag(ctx, w->seq_idx, batch, &fopts, 0, &ffr[0], &longest)) != 0 ||
@@ -734,7 +813,7 @@ static void *gpu_worker(void *p)
             goto out;
         }
     }
-    if (xl)
+    if (xl && !sg)
     {
         uint32_t longest = 0;
         if ((rc = B->alloc_xlat(ctx, w->seq_idx, batch, xl_extra, &xfr[0], &longest)) != 0 ||
@@ -753,7 +832,7 @@ static void *gpu_worker(void *p)
             goto out;
         }
     }
-    if (enc)
+    if (enc && !sg)
     {
         uint32_t longest = 0;
         /* from the fragment buffer: sized for the fragments, and the longest frame is a fragment's */
@@ -924,9 +1003,40 @@ static void *gpu_worker(void *p)
                 break;
             }
         }
+        if (sg)
+        {
+            if ((rc = B->segment(ctx, fr[cur], &sgopts, sfr[cur])) != 0)
+            {
+                fprintf(stderr, "[%d] Error segmenting frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
+                last_error = rc;
+                break;
+            }
+            /* segments are plain frames the verifier parses: the sequence's own checks again */
+            if (w->cmd.verify)
+            {
+                uint64_t bad = 0, first_bad = 0;
+                if ((rc = B->verify(ctx, sfr[cur], vchecks, &bad, &first_bad)) != 0)
+                {
+                    fprintf(stderr, "[%d] Error verifying frames on GPU %d :: %s.\n", seq_num, w->gpu,
+                            pbgpu_strerror(rc));
+                    last_error = rc;
+                    break;
+                }
+                if (bad)
+                {
+                    __atomic_add_fetch(&verified_bad[w->seq_idx], bad, __ATOMIC_RELAXED);
+                    pb_verify_failed_msg(seq_num, bad, first_bad,
+                                         (step * (uint64_t)w->n_shards + (uint64_t)w->shard) * batch);
+                    last_error = PBGPU_EIO;
+                    verify_failed[w->seq_idx] = 1;
+                    break;
+                }
+            }
+        }
+        void *const sf = sg ? sfr[cur] : fr[cur]; /* the batch as it is fragmented or translated */
         if (frg)
         {
-            if ((rc = B->fragment(ctx, fr[cur], &fopts, ffr[cur])) != 0)
+            if ((rc = B->fragment(ctx, sf, &fopts, ffr[cur])) != 0)
             {
                 fprintf(stderr, "[%d] Error fragmenting frames on GPU %d :: %s.\n", seq_num, w->gpu, pbgpu_strerror(rc));
                 last_error = rc;
@@ -954,14 +1064,14 @@ static void *gpu_worker(void *p)
                 }
             }
         }
-        if (xl && (rc = B->xlat(ctx, fr[cur], &xopts, xfr[cur])) != 0)
+        if (xl && (rc = B->xlat(ctx, sf, &xopts, xfr[cur])) != 0)
         {
             fprintf(stderr, "[%d] Error translating frames to IPv6 on GPU %d :: %s%s.\n", seq_num, w->gpu, pbgpu_strerror(rc),
                     rc == PBGPU_EINVAL ? " (a frame that is not UDP, TCP or an ICMP echo?)" : "");
             last_error = rc;
             break;
         }
-        void *const bf = xl ? xfr[cur] : frg ? ffr[cur] : fr[cur]; /* the batch as it is encapsulated or landed */
+        void *const bf = xl ? xfr[cur] : frg ? ffr[cur] : sf; /* the batch as it is encapsulated or landed */
         if (enc)
         {
             if ((rc = B->encap(ctx, bf, &eopts, efr[cur])) != 0)
@@ -1262,6 +1372,8 @@ out:
             B->free_frames(ctx, ffr[i]);
         if (xfr[i])
             B->free_frames(ctx, xfr[i]);
+        if (sfr[i])
+            B->free_frames(ctx, sfr[i]);
     }
     if (ctx)
         B->close(ctx);
@@ -1311,6 +1423,12 @@ void seq_send(const char *interface, pb_sequence_t seq, uint16_t seqc, struct cm
     if (encap_on && (builder->encap == NULL || builder->alloc_encap == NULL))
     {
         fprintf(stderr, "[%d] --encap: this frame builder cannot encapsulate.\n", seq_cnt + 1);
+        last_error = PBGPU_ENOTSUP;
+        return;
+    }
+    if (seg_on && (builder->segment == NULL || builder->alloc_seg == NULL))
+    {
+        fprintf(stderr, "[%d] --segment: this frame builder cannot segment.\n", seq_cnt + 1);
         last_error = PBGPU_ENOTSUP;
         return;
     }

@@ -53,6 +53,17 @@ const pbgpu_encap_opts *pb_get_encap(void);
  * default). */
 void pb_set_fragment(const pbgpu_frag_opts *opts);
 const pbgpu_frag_opts *pb_get_fragment(void);
+/* --segment MSS[:fixedid] (main_gpu.c's own option): every built batch's TCP and UDP frames are cut
+ * into segments of at most MSS payload bytes on the GPU (pbgpu_segment) after the batch is stamped and
+ * verified and before it is verified again, fragmented, translated, encapsulated, landed or packed.
+ * NULL: none (the default). */
+void pb_set_segment(const pbgpu_seg_opts *opts);
+const pbgpu_seg_opts *pb_get_segment(void);
+/* What --segment makes of a sequence's frames, the longest of which is `longest` bytes: NO_L4_CSUM is
+ * added to *opts exactly when the sequence's l4_csum is 0; *per_frame = the segments a frame can
+ * become at the most, *piece = the longest frame afterwards (an ICMP sequence is not cut). */
+void pb_seg_plan_for(const pb_sequence_t *seq, pbgpu_seg_opts *opts, uint32_t longest, uint32_t *per_frame,
+                     uint32_t *piece);
 /* --stamp head[:OFF] | tail[:OFF] (main_gpu.c's own option): every built batch is stamped on the GPU
  * (pbgpu_stamp) before it is verified, fragmented, encapsulated, landed or packed, so --verify proves
  * the updated checksums and the fragments of one packet share one stamp.  `opts` carries the offset,
@@ -165,6 +176,13 @@ typedef struct pb_builder
     /* --verifywire: the batch in `frames` checked as it leaves (pbgpu_verify_wire over all of its
      * frames).  NULL: --verifywire is refused. */
     int (*verify_wire)(void *h, void *frames, const pbgpu_wire_opts *opts, pbgpu_wire_result *res);
+    /* --segment: a buffer for n_iter iterations' frames when each can become up to per_frame frames and
+     * `extra` more bytes in all (the segments' headers, and what fragmenting, translating and
+     * encapsulating them adds); the built batch `src` segmented into such a buffer (pbgpu_segment),
+     * which then verifies, fragments, translates, encapsulates and lands like a built one.  NULL:
+     * --segment is refused. */
+    int (*alloc_seg)(void *h, uint16_t seq_idx, uint64_t n_iter, uint32_t per_frame, uint32_t extra, void **frames);
+    int (*segment)(void *h, void *src, const pbgpu_seg_opts *opts, void *dst);
 } pb_builder_t;
 
 void pb_set_builder(const pb_builder_t *b); /* NULL: libpbgpu */

@@ -246,6 +246,40 @@ class FragResult(C.Structure):
     ]
 
 
+SEG_NO_L4_CSUM = 1  # the L4 checksum field is copied from the source; no payload byte is summed
+SEG_FIXED_ID = 2    # every segment keeps the source's IPv4 ID
+
+
+class SegOpts(C.Structure):
+    """pbgpu_seg_opts (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("mss", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class SegResult(C.Structure):
+    """pbgpu_seg_result (include/pbgpu.h)."""
+
+    _fields_ = [
+        ("n_in", C.c_uint64),
+        ("n_out", C.c_uint64),
+        ("n_split_tcp", C.c_uint64),
+        ("n_split_udp", C.c_uint64),
+        ("n_other", C.c_uint64),
+        ("out_bytes", C.c_uint64),
+        ("out_min_len", C.c_uint32),
+        ("out_max_len", C.c_uint32),
+        ("device_ms", C.c_double),
+    ]
+
+
+def _seg_flags(no_l4_csum: bool, fixed_id: bool) -> int:
+    return (SEG_NO_L4_CSUM if no_l4_csum else 0) | (SEG_FIXED_ID if fixed_id else 0)
+
+
 STAMP_TAIL = 1     # position counted back from the frame's end
 STAMP_NO_CSUM = 2  # leave the L4 checksum as it is
 
@@ -522,6 +556,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_fragment_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
         "pbgpu_fragment_bound": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), U64P, U64P]),
         "pbgpu_fragment": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(FragOpts), FP, C.POINTER(FragResult)]),
+        "pbgpu_segment_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(SegOpts), U64P, U64P]),
+        "pbgpu_segment_bound": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(SegOpts), U64P, U64P]),
+        "pbgpu_segment": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(SegOpts), FP, C.POINTER(SegResult)]),
         "pbgpu_stamp": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(StampOpts), C.POINTER(StampResult)]),
         "pbgpu_xlat46_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), U64P, U64P]),
         "pbgpu_xlat46": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(XlatOpts), FP, C.POINTER(XlatResult)]),
@@ -698,6 +735,19 @@ class FrameBuffer:
         res = FragResult()
         _check(self.ctx.lib.pbgpu_fragment(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(res)),
                "fragment")
+        return res
+
+    def segment(self, dst: "FrameBuffer", first: int = 0, n: Optional[int] = None, mss: int = 1460,
+                no_l4_csum: bool = False, fixed_id: bool = False) -> SegResult:
+        """Cuts the TCP and UDP frames among [first, first + n) (n None: to the last frame) into
+        segments of at most mss payload bytes, each with its own headers and checksums, into dst; dst
+        is then a frames buffer like a built one.  Returns the SegResult."""
+        if n is None:
+            n = int(self.f.n_frames) - first
+        opts = SegOpts(mss, _seg_flags(no_l4_csum, fixed_id), 0)
+        res = SegResult()
+        _check(self.ctx.lib.pbgpu_segment(self.ctx.h, self.ptr, first, n, C.byref(opts), dst.ptr, C.byref(res)),
+               "segment")
         return res
 
     def stamp(self, first: int = 0, n: Optional[int] = None, t0_ns: int = 0, step_ps: int = 0, first_index: int = 0,
@@ -890,6 +940,26 @@ class GpuContext:
                        ignore_df: bool = False):
         """An upper bound of (frames, bytes) from fb's longest frame, with no device work."""
         return self._frag_sizes(self.lib.pbgpu_fragment_bound, "fragment_bound", fb, first, n, mtu, ignore_df)
+
+    def _seg_sizes(self, fn, what: str, fb: "FrameBuffer", first: int, n: Optional[int], mss: int, flags: int):
+        if n is None:
+            n = int(fb.f.n_frames) - first
+        opts = SegOpts(mss, flags, 0)
+        frames, nbytes = C.c_uint64(), C.c_uint64()
+        _check(fn(self.h, fb.ptr, first, n, C.byref(opts), C.byref(frames), C.byref(nbytes)), what)
+        return int(frames.value), int(nbytes.value)
+
+    def segment_size(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, mss: int = 1460,
+                     no_l4_csum: bool = False, fixed_id: bool = False):
+        """The exact (frames, bytes) FrameBuffer.segment would write (count and scan passes only)."""
+        return self._seg_sizes(self.lib.pbgpu_segment_size, "segment_size", fb, first, n, mss,
+                               _seg_flags(no_l4_csum, fixed_id))
+
+    def segment_bound(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, mss: int = 1460,
+                      no_l4_csum: bool = False, fixed_id: bool = False):
+        """An upper bound of (frames, bytes) from fb's longest frame, with no device work."""
+        return self._seg_sizes(self.lib.pbgpu_segment_bound, "segment_bound", fb, first, n, mss,
+                               _seg_flags(no_l4_csum, fixed_id))
 
     def kernel_name(self, idx: int) -> str:
         buf = C.create_string_buffer(96)
