@@ -631,6 +631,11 @@ const char *pbgpu_fill_shape_name(int shape);
  * plain read shape - aligned 16-B loads, 4 KiB per workgroup, an XOR of the loaded words stored
  * once per workgroup - and their mean device time.  What pbgpu_verify is measured against. */
 int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_t reps, double *ms_per_launch);
+/* The launch shape of the repack writers (pcap pack, encap, fragment, segment, xlat46) of this
+ * context over an output of `npages` 4-KiB pages: pages per workgroup and workgroups.  per is
+ * clamp(npages / 16384, 1, 32), or PBGPU_RP_PER (1 to 32) as read at pbgpu_open, and more where the
+ * grid would pass 2^24.  Launches nothing. */
+int pbgpu_page_grid(pbgpu_ctx *ctx, uint64_t npages, uint32_t *per, uint32_t *grid);
 
 /* Name of the frame-build kernel variant a loaded sequence launches
  * (as rocprofv3 reports it). */

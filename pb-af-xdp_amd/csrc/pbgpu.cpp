@@ -83,7 +83,7 @@ namespace
 {
 
 // Shape overrides for the parity tests and A/B runs (PBGPU_* environment).  They are read in
-// one place, read_opts(): at pbgpu_open into the context (landing and batch options) and at
+// one place, read_opts(): at pbgpu_open into the context (landing, batch and repack options) and at
 // pbgpu_load_sequence into the slot (kernel shapes), so the build path never reads the
 // environment and a loaded sequence's shape is fixed.  Every selectable shape is parity-tested
 // (tests/test_gpu_kernels.py).
@@ -133,6 +133,8 @@ struct pb_opts
                                   // 43 vs 49 GB/s in bench.py's build + land on another)
     uint32_t vp_pages_pct = 0; // PBGPU_VP_PAGES_PCT: pb_vpage_kernel's grid as a percentage of the
                                // expected pages (tests: a short grid, so waves take several pages)
+    uint32_t rp_per = 0;       // PBGPU_RP_PER: pages per workgroup of the five repack writers, 1 to 32
+                               // (tests: several pages per workgroup at outputs of a few MB)
 };
 
 uint32_t opt_u32(const char *name)
@@ -189,6 +191,9 @@ pb_opts read_opts()
     o.umem_dma = getenv("PBGPU_UMEM_DMA") != NULL;
     o.alloc_vmm = !opt_is("PBGPU_ALLOC", "malloc");
     o.vp_pages_pct = opt_u32("PBGPU_VP_PAGES_PCT");
+    o.rp_per = opt_u32("PBGPU_RP_PER");
+    if (o.rp_per > 32)
+        o.rp_per = 0;
     if (getenv("PBGPU_LAND_DMA_MIN"))
         o.land_dma_min = (uint32_t)atoi(getenv("PBGPU_LAND_DMA_MIN"));
     if (opt_u32("PBGPU_ALLOC_CHUNK_MB"))
@@ -284,7 +289,7 @@ struct pbgpu_ctx
     hipStream_t stream = nullptr;      // frame builds
     hipStream_t land_stream = nullptr; // UMEM landing: overlaps the next build (pbgpu_copy_to_umem)
     bool land_events = false;          // set by the first landing: builds then record a completion event
-    pb_opts opt;                       // read at pbgpu_open: landing, stream and batch options
+    pb_opts opt;                       // read at pbgpu_open: landing, stream, batch and repack options
     uint2 *d_jump = nullptr;
     uint2 *d_lcg48 = nullptr;
     uint32_t *d_orbit = nullptr; // pb_vline_kernel: LCG-orbit prefix sums (built on first use, 2 MiB)
@@ -1835,11 +1840,14 @@ static int scratch_reserve(void **ptr, uint64_t *cap, uint64_t need, size_t byte
 }
 
 // Pages per workgroup of a launch over 4-KiB pages: they grow with the launch (at least 16384
-// workgroups in a large one, 32 pages at the most), and further where the grid would pass 2^24.
-static int page_grid(uint64_t npages, uint32_t *per_out, uint32_t *grid)
+// workgroups in a large one, 32 pages at the most), or are `forced` (1 to 32; 0: by the rule), and
+// grow further where the grid would pass 2^24.
+static int page_grid(uint64_t npages, uint32_t forced, uint32_t *per_out, uint32_t *grid)
 {
     uint64_t per = npages / 16384;
     per = per < 1 ? 1 : (per > 32 ? 32 : per);
+    if (forced)
+        per = forced;
     if ((npages + per - 1) / per > (1ull << 24))
         per = (npages + (1ull << 24) - 1) >> 24;
     if (per > 0xFFFFFFFFull)
@@ -1847,6 +1855,13 @@ static int page_grid(uint64_t npages, uint32_t *per_out, uint32_t *grid)
     *per_out = (uint32_t)per;
     *grid = (uint32_t)((npages + per - 1) / per);
     return PBGPU_OK;
+}
+
+int pbgpu_page_grid(pbgpu_ctx *ctx, uint64_t npages, uint32_t *per, uint32_t *grid)
+{
+    if (ctx == NULL || per == NULL || grid == NULL)
+        return PBGPU_EINVAL;
+    return page_grid(npages, ctx->opt.rp_per, per, grid);
 }
 
 // Frames [first, first + n) of a buffer that holds frames (reserved: set by the first build or upload)
@@ -2467,7 +2482,7 @@ static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint6
         A->npages = ((b1 - 1) >> 12) - A->page0 + 1;
         // pages per wave. n <= n_frames < 2^32 of at most 128 B: npages <= 2^27 + 1, far from
         // page_grid's grid cap and its refusal
-        (void)page_grid(A->npages, &A->wgf, grid);
+        (void)page_grid(A->npages, 0, &A->wgf, grid);
         return 0;
     }
     return vst_shape(f, n, mean, &A->wgf, &A->bf, grid);
@@ -2792,7 +2807,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
         A.step_ps = opts->step_ps;
         A.first_index = opts->first_index;
         uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
         timing_pair tp;
         PBCHK(timed_begin(ctx, &tp));
         HIPCHK(pbk_launch_pcap(&A, grid, st));
@@ -2920,7 +2935,7 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
             A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
                        ((uint32_t)t[4 * i + 3] << 24);
         uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
         timing_pair tp;
         PBCHK(timed_begin(ctx, &tp));
         HIPCHK(pbk_launch_encap(&A, grid, st)); // variable length: dst->offsets by a launch of its own first
@@ -3078,7 +3093,7 @@ int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint
         A.total = total;
         A.end16 = end16;
         uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
         HIPCHK(pbk_launch_frag(&A, copy ? 2 : 1, grid, st));
         PBCHK(timed_stop(ctx, tp));
         PBCHK(timed_ms(ctx, tp, &ms));
@@ -3248,7 +3263,7 @@ int pbgpu_segment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint6
     if (n)
     {
         uint32_t grid = 0, per = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, &per, &grid));
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &per, &grid));
         if (copy)
         {
             pb_fgargs F;
@@ -3489,7 +3504,7 @@ int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64
         A.dst = dst->data;
         A.dst_offsets = dst->offsets;
         uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, &A.per, &grid));
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
         HIPCHK(pbk_launch_xlat(&A, 1, grid, st)); // variable length: dst->offsets by a launch of its own first
         PBCHK(timed_stop(ctx, tp));
         PBCHK(timed_ms(ctx, tp, &ms));

@@ -548,6 +548,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_verify": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(VerifyResult), P]),
         "pbgpu_frames_upload": (C.c_int, [P, FP, P, U64P, C.c_uint32, C.c_uint64]),
         "pbgpu_read_probe_at": (C.c_int, [P, P, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
+        "pbgpu_page_grid": (C.c_int, [P, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "pbgpu_pcap_size": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.c_uint32, U64P]),
         "pbgpu_pcap_pack": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(PcapOpts), FP, U64P,
                                       C.POINTER(C.c_double)]),
@@ -896,6 +897,13 @@ class GpuContext:
         ms = C.c_double()
         _check(self.lib.pbgpu_read_probe_at(self.h, fb.f.data, nbytes, reps, C.byref(ms)), "read_probe_at")
         return float(ms.value)
+
+    def page_grid(self, npages: int):
+        """(pages per workgroup, workgroups) of this context's repack writers (pcap_pack, encap,
+        fragment, segment, xlat46) over an output of npages 4-KiB pages; launches nothing."""
+        per, grid = C.c_uint32(), C.c_uint32()
+        _check(self.lib.pbgpu_page_grid(self.h, npages, C.byref(per), C.byref(grid)), "page_grid")
+        return int(per.value), int(grid.value)
 
     def pcap_size(self, fb: "FrameBuffer", first: int = 0, n: Optional[int] = None, flags: int = PCAP_FILE_HEADER) -> int:
         """Bytes of the pcap stream of fb's frames [first, first + n) (n None: to the last frame)."""

@@ -135,14 +135,18 @@ def test_fixed_uploaded(ctx, name, L, n):
 
 
 # ------------------------------------------------------------------ 2. variable lengths, uploaded
-@pytest.fixture(scope="module")
-def random3000(ctx):
+def random3000_frames():
     """14..300 B with many 14-B frames: more records than one LDS window, up to 227 to a page."""
     rng = np.random.default_rng(99)
     lens = rng.integers(14, 301, 3000)
     lens[rng.random(3000) < 0.5] = 14
     lens[1000:1700] = 14
-    data, off = lens_to_frames(lens, 2)
+    return lens_to_frames(lens, 2)
+
+
+@pytest.fixture(scope="module")
+def random3000(ctx):
+    data, off = random3000_frames()
     fb = uploaded(ctx, data, off=off)
     yield fb, split(data, off), off
     fb.free()

@@ -177,10 +177,14 @@ def test_variable_edge_lengths(ctx, hdr):
         fb.free()
 
 
+def random3000_frames():
+    lens = np.random.default_rng(99).integers(0, 201, 3000)
+    return lens_to_frames(lens, 2)
+
+
 @pytest.fixture(scope="module")
 def random3000(ctx):
-    lens = np.random.default_rng(99).integers(0, 201, 3000)
-    data, off = lens_to_frames(lens, 2)
+    data, off = random3000_frames()
     fb = uploaded(ctx, data, off=off)
     yield fb, split(data, off), off
     fb.free()

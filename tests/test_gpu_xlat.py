@@ -159,11 +159,15 @@ def mixed_frames(lens, seed):
     return out
 
 
-@pytest.fixture(scope="module")
-def mixed1000(ctx):
+def mixed1000_frames():
     """1,000 frames of mixed protocols, 42..1600 B: more records than one LDS window."""
     lens = np.random.default_rng(99).integers(42, 1601, 1000)
-    frames = mixed_frames(lens, 2)
+    return mixed_frames(lens, 2)
+
+
+@pytest.fixture(scope="module")
+def mixed1000(ctx):
+    frames = mixed1000_frames()
     fb = upload_frames(ctx, frames)
     yield fb, frames
     fb.free()
