@@ -172,7 +172,30 @@ def _edge_cases():
     c = c3_udp_var()
     c["payloads"] = [{"length": {"min": 0, "max": 1}}]
     e["udp_tiny_var"] = c
+
+    # long static payloads (sequence.c:264-361): a request sent verbatim, and static payloads of
+    # every source among random ones (the staged kernels gather them from the device blob)
+    c = c4_tcp_syn()
+    c["tcp"] = {"sport": 0, "dport": 80, "psh": 1, "ack": 1}
+    c["payloads"] = [{"exact": _request_1400(), "isstring": 1}]
+    e["tcp_static_string_1400"] = c
+
+    c = c2_udp_64()
+    c["payloads"] = [{"exact": " ".join("%02x" % ((i * 7 + 3) & 0xFF) for i in range(1400))},
+                     {"length": {"min": 100, "max": 1400}},
+                     {"isstatic": 1, "length": {"min": 900, "max": 1000}},
+                     {"exact": "".join(chr(33 + (5 * i) % 94) for i in range(300)), "isstring": 1}]
+    e["udp_mixed_long"] = c
     return e
+
+
+def _request_1400():
+    """An HTTP request of exactly 1400 characters."""
+    head = "POST /api/v1/items HTTP/1.1\r\nHost: %s\r\nContent-Type: text/plain\r\nContent-Length: %d\r\n\r\n"
+    body = 1400 - len(head % (DIP, 1000))
+    text = head % (DIP, body) + "".join(chr(97 + (3 * i) % 26) for i in range(body))
+    assert len(text) == 1400
+    return text
 
 
 EDGE = _edge_cases()

@@ -83,26 +83,51 @@ def mac(s):
     return bytes(6) if not s else bytes(int(x, 16) for x in s.split(":"))
 
 
+HEXDIGITS = b"0123456789abcdefABCDEF"
+
+
+def scan_2hhx(tok):
+    """sscanf(tok, "%2hhx", &b) from b = 0 (sequence.c:328), as C specifies strtoul-style input
+    under a field width: white space is skipped and does not count, then at most two characters
+    are taken: an optional sign, an optional 0x / 0X, hex digits.  A 0 whose x is cut off or not
+    followed by a digit still converts (to 0); no digit at all leaves b as it was."""
+    s = tok.lstrip(b" \t\n\v\f\r")
+    width, i, neg, digits = 2, 0, False, b""
+    if s[i:i + 1] in (b"+", b"-"):
+        neg = s[i:i + 1] == b"-"
+        i, width = i + 1, width - 1
+    if width and s[i:i + 1] == b"0":
+        digits = b"0"
+        i, width = i + 1, width - 1
+        if width and s[i:i + 1] in (b"x", b"X"):
+            i, width = i + 1, width - 1
+    while width and s[i:i + 1] and s[i:i + 1] in HEXDIGITS:
+        digits += s[i:i + 1]
+        i, width = i + 1, width - 1
+    if not digits:
+        return 0
+    v = int(digits, 16)
+    return (-v if neg else v) & 0xFF
+
+
 def exact_bytes(p):
+    """A payload's `exact` text as bytes (sequence.c:269-337): the config string as the loaders
+    pass it (UTF-8) or the file's bytes (a file that cannot be opened is an empty text), cut at the
+    first NUL as strlen / strtok_r see it; a string verbatim, else one byte per token between
+    spaces (strtok_r splits at ' ' only, so a line break stays inside its token)."""
     text = p["exact"]
     if p.get("isfile"):
         try:
             with open(text, "rb") as f:
-                text = f.read().split(b"\0")[0].decode("latin-1")
+                text = f.read()
         except OSError:
-            text = ""
+            text = b""
+    elif isinstance(text, str):
+        text = text.encode()
+    text = text.split(b"\0")[0]
     if p.get("isstring"):
-        return text.encode("latin-1")
-    out = []
-    for tok in [t for t in text.split(" ") if t]:
-        h = ""
-        for ch in tok[:2]:
-            if ch in "0123456789abcdefABCDEF":
-                h += ch
-            else:
-                break
-        out.append(int(h, 16) if h else 0)
-    return bytes(out)
+        return text
+    return bytes(scan_2hhx(tok) for tok in text.split(b" ") if tok)
 
 
 def build(cfg, seq_idx, first_iter, n_iter, seed_base, literal=False, single_fold=False):

@@ -85,6 +85,7 @@ CASES = [
     # pages of frames cut at the page edges
     Case("xpage_tcp60", "pb_xpage_kernel", pc.get("c4_tcp_syn"), {}, 0, TCP60),
     Case("xpage_tcp60_fa64", "pb_xpage_kernel", pc.get("c4_tcp_syn"), {"PBGPU_XP_FA64": "1"}, 0, TCP60),
+    Case("xpage_tcp60_static", "pb_xpage_kernel", _static("c4_tcp_syn", 6), {}, 0, TCP60),
     Case("xpage_icmp98", "pb_xpage_kernel", pc.get("c5_icmp_echo"), {}, 0, ICMP98),
     # (106-B static UDP takes the page kernel's 2-mod-4 form, not pb_stage_kernel; 2048 frames: 53 pages)
     Case("xpage_udp_static106", "pb_xpage_kernel", pc.get("c1_udp_static_106"), {}, 0,
@@ -99,6 +100,8 @@ CASES = [
     Case("fstage_1500", "pb_fstage_kernel", _udp(1500), {}, 0, (1, 15, 17, 32, 65, 513)),
     Case("fstage_1508", "pb_fstage_kernel", _udp(1508), {}, 0, (1, 15, 17, 32, 65, 513)),
     Case("stage_static242", "pb_stage_kernel", _static("c1_udp_static_106", 200), {}, 0, (1, 3, 8, 17, 65, 513)),
+    # a static payload gathered from the device blob: 1500 B is 12 mod 16, four frames end on a chunk
+    Case("stage_static1500", "pb_stage_kernel", _static("c2_udp_64", 1458), {}, 0, (1, 3, 4, 17, 65, 513)),
     Case("stage_literal1500", "pb_stage_kernel", _udp(1500), {}, 1, (1, 4, 15, 17, 65, 513)),
     Case("stage_multi_payload", "pb_stage_kernel", pc.get("udp_multi_payload"), {}, 0, (1, 3, 64, 65, 513)),
     Case("vstage_fixed1501", "pb_vstage_kernel", _udp(1501), {}, 0, (1, 7, 16, 33, 129, 513)),
@@ -116,6 +119,8 @@ CASES = [
          (1, 3, V33_PAGE, V33_PAGES, 253, 1740, 1772)),
     Case("vpage_64_1500", "pb_vpage_kernel", _pl("c3_udp_var", 64, 1500), VPAGE, 0, (1, 3, 160, 253)),
     Case("gpf_65042", "pb_gpf_kernel", _udp(65042), {}, 0, (1, 3, 8)),
+    # the longest frame there is (PB_MAX_PCKT_LEN), its payload static
+    Case("gpf_static65535", "pb_gpf_kernel", _static("c2_udp_64", 65493), {}, 0, (1, 3, 8)),
 ]
 BY_ID = {c.id: c for c in CASES}
 # families whose every frame length is a multiple of 16
