@@ -304,52 +304,15 @@ struct pb_enargs
     uint32_t tpl[PB_EN_TDW]; // the header bytes, little-endian dwords, zero padded (fixed length: lengths and checksum filled in)
 };
 
-// ---- IPv4 fragmentation (pbgpu_fragment: pb_frag_*_kernel, DESIGN.md 5.11) ----
-// Output record f = fragment i of source frame first + j (or the whole frame, copied).
+// ---- cutting frames into pieces (pbgpu_fragment, pbgpu_segment: pb_cut_*) ----
+// Output record f = piece i (fragment or segment) of source frame first + j, or the whole frame,
+// copied.  The two calls share the count, map and writer scaffold, its sizes and its arguments.
 #define PB_FG_WT 256u                // threads per workgroup: one source frame each (count, map), one 16-B chunk each (writer)
 #define PB_FG_CB 16u                 // count: rows of PB_FG_WT frames per workgroup
 #define PB_FG_WIN 320u               // writer: record positions kept in LDS (a page touches at most 294 records of >= 14 B, and one entry ends the last)
 #define PB_FG_HREC 300u              // header slots per page
-#define PB_FG_HDW 10u                // a staged 34-B header, moved to its destination's alignment: up to 37 bytes
-#define PB_FG_IGNORE_DF 1u           // pb_fgargs.flags, as PBGPU_FRAG_IGNORE_DF
-// map entry of an output record: the source frame's byte offset in src (48 bits), then
-#define PB_FG_M_ISH 48u              // ... the fragment index i (11 bits)
-#define PB_FG_M_SPLIT (1u << 11)     // ... (entry >> 48) bit: the record is a fragment (its header is staged and patched)
-#define PB_FG_M_LAST (1u << 12)      // ... the frame's last fragment (MF as the source has it)
-#define PB_FG_RES_DW 8u              // result words: n_out, n_split, n_df, n_other, min len, max len
-struct pb_fgargs
-{
-    const uint8_t *src;      // src->data (16-B aligned)
-    const uint64_t *offsets; // src->offsets (variable length), null for fixed length
-    uint8_t *dst;            // dst->data (16-B aligned)
-    uint64_t *dst_offsets;   // dst->offsets
-    uint64_t first, n;       // source frames [first, first + n)
-    uint64_t n_out;          // output records (writer, map)
-    uint64_t total, end16;   // output bytes, and rounded up to 16: what is written
-    uint32_t fixed_len;
-    uint32_t mtu, C;         // C = (mtu - 20) & ~7: data bytes of a full fragment
-    pb_div cdiv;             // division by C
-    uint32_t flags;
-    uint32_t per;            // writer: pages per workgroup
-    uint32_t *kcnt;          // K per source frame of the range
-    unsigned long long *bsum; // K summed per count workgroup, then their exclusive scan
-    unsigned long long *res; // PB_FG_RES_DW words
-    uint64_t *map;           // n_out entries
-};
-
-// ---- L4 segmentation (pbgpu_segment: pb_seg_*_kernel, DESIGN.md 5.15) ----
-// Output record f = segment i of source frame first + j (or the whole frame, copied).  The count,
-// window and page sizes are the fragmenter's (PB_FG_WT, PB_FG_CB, PB_FG_WIN, PB_FG_HREC).
-#define PB_SG_HDW 25u                // a staged 34 + H <= 94-B header, moved to its destination's alignment: up to 97 bytes
-#define PB_SG_NO_L4 1u               // pb_sgargs.flags, as PBGPU_SEG_NO_L4_CSUM / _FIXED_ID
-#define PB_SG_FIXED_ID 2u
-// map entry of an output record: the source frame's byte offset in src (44 bits), then
-#define PB_SG_M_ISH 44u              // ... the segment index i (13 bits: at most 8,187 segments)
-#define PB_SG_M_HSH 13u              // ... (entry >> 44) bits 13..16: H / 4 (2 UDP, 5..15 TCP)
-#define PB_SG_M_SEG (1u << 17)       // ... the record is a segment (its header is staged and patched)
-#define PB_SG_M_LAST (1u << 18)      // ... the frame's last segment (FIN and PSH as the source has them)
-#define PB_SG_RES_DW 8u              // result words: n_out, n_split_tcp, n_split_udp, n_other, min len, max len, inserted bytes, the largest H / 4 split
-struct pb_sgargs
+#define PB_FG_RES_DW 8u              // result words: n_out, three counts by kind, min len, max len; segment: inserted bytes, the largest H / 4 split
+struct pb_cutargs
 {
     const uint8_t *src;      // src->data (16-B aligned)
     const uint64_t *offsets; // src->offsets (variable length), null for fixed length
@@ -359,18 +322,39 @@ struct pb_sgargs
     uint64_t n_out;          // output records (map, sum, writer)
     uint64_t total, end16;   // output bytes, and rounded up to 16: what is written
     uint32_t fixed_len;
-    uint32_t mss;
-    pb_div mdiv;             // division by mss
-    uint32_t flags;
+    uint32_t cut;            // data bytes of a full piece: C = (mtu - 20) & ~7, or mss
+    pb_div cdiv;             // division by cut
+    uint32_t flags;          // PB_FG_* or PB_SG_*
     uint32_t per;            // writer: pages per workgroup
-    uint32_t hdw;            // writer: dwords per staged header slot, 10 + the largest H / 4 (<= PB_SG_HDW)
-    uint32_t *kcnt;          // K | H / 4 << 16 per source frame of the range
+    uint32_t mtu;            // fragment
+    uint32_t hdw;            // segment, writer: dwords per staged header slot, 10 + the largest H / 4 (<= PB_SG_HDW)
+    uint32_t *kcnt;          // per source frame of the range K (fragment), K | H / 4 << 16 (segment)
     unsigned long long *bsum; // K summed per row of PB_FG_WT frames, then their exclusive scan
-    unsigned long long *xsum; // the inserted bytes (K - 1)(34 + H) likewise
-    unsigned long long *res; // PB_SG_RES_DW words
+    unsigned long long *res; // PB_FG_RES_DW words
     uint64_t *map;           // n_out entries
-    uint32_t *psum;          // n_out folded payload sums (frame domain), segments' only
+    unsigned long long *xsum; // segment: the inserted bytes (K - 1)(34 + H) per row, as bsum
+    uint32_t *psum;          // segment: n_out folded payload sums (frame domain), segments' only
 };
+
+// ---- IPv4 fragmentation (pbgpu_fragment: pb_frag_*_kernel, DESIGN.md 5.11) ----
+#define PB_FG_HDW 10u                // a staged 34-B header, moved to its destination's alignment: up to 37 bytes
+#define PB_FG_IGNORE_DF 1u           // pb_cutargs.flags, as PBGPU_FRAG_IGNORE_DF
+// map entry of an output record: the source frame's byte offset in src (48 bits), then
+#define PB_FG_M_ISH 48u              // ... the fragment index i (11 bits)
+#define PB_FG_M_SPLIT (1u << 11)     // ... (entry >> 48) bit: the record is a fragment (its header is staged and patched)
+#define PB_FG_M_LAST (1u << 12)      // ... the frame's last fragment (MF as the source has it)
+// result words 1..3: n_split, n_df, n_other
+
+// ---- L4 segmentation (pbgpu_segment: pb_seg_*_kernel, DESIGN.md 5.15) ----
+#define PB_SG_HDW 25u                // a staged 34 + H <= 94-B header, moved to its destination's alignment: up to 97 bytes
+#define PB_SG_NO_L4 1u               // pb_cutargs.flags, as PBGPU_SEG_NO_L4_CSUM / _FIXED_ID
+#define PB_SG_FIXED_ID 2u
+// map entry of an output record: the source frame's byte offset in src (44 bits), then
+#define PB_SG_M_ISH 44u              // ... the segment index i (13 bits: at most 8,187 segments)
+#define PB_SG_M_HSH 13u              // ... (entry >> 44) bits 13..16: H / 4 (2 UDP, 5..15 TCP)
+#define PB_SG_M_SEG (1u << 17)       // ... the record is a segment (its header is staged and patched)
+#define PB_SG_M_LAST (1u << 18)      // ... the frame's last segment (FIN and PSH as the source has them)
+// result words 1..3: n_split_tcp, n_split_udp, n_other
 
 // ---- stamping (pbgpu_stamp: pb_stamp_kernel) ----
 // In place: frame first + j gets 16 bytes and its L4 checksum field rewritten, by one lane.

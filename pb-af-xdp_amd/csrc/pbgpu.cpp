@@ -52,8 +52,10 @@ extern "C" hipError_t pbk_launch_wfold(const uint32_t *rec, uint32_t nrec, unsig
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
-extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st);
-extern "C" hipError_t pbk_launch_seg(const pb_sgargs *A, int stage, int G, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_frag(const pb_cutargs *A, int stage, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_seg(const pb_cutargs *A, int stage, int G, uint32_t grid, hipStream_t st);
+extern "C" hipError_t pbk_launch_cut_copy(const uint8_t *src, uint8_t *dst, uint64_t a0, uint64_t total,
+                                          uint64_t end16, uint32_t per, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st);
 extern "C" hipError_t pbk_launch_xlat(const pb_xlargs *A, int stage, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen, uint32_t wlen, uint32_t n,
@@ -310,20 +312,17 @@ struct pbgpu_ctx
     unsigned long long *h_wres = nullptr, *d_wres = nullptr; // pbgpu_verify_wire's folded result, as h_vres
     uint8_t *d_vcodes = nullptr;
     uint64_t vcodes_cap = 0;
-    // pbgpu_fragment: the count pass's scratch (result words, workgroup sums, K per source frame)
-    // and the map (one entry per output record), each grown on demand
-    uint8_t *d_fg_cnt = nullptr;
-    uint64_t fg_cnt_cap = 0; // source frames
-    uint64_t *d_fg_map = nullptr;
-    uint64_t fg_map_cap = 0; // output records
-    // pbgpu_segment: the count pass's scratch (result words, two row sums, K and H per source frame),
-    // the map entries and the slice sums of the output records
-    uint8_t *d_sg_cnt = nullptr;
-    uint64_t sg_cnt_cap = 0; // source frames
-    uint64_t *d_sg_map = nullptr;
-    uint64_t sg_map_cap = 0; // output records
-    uint32_t *d_sg_psum = nullptr;
-    uint64_t sg_psum_cap = 0; // output records
+    // pbgpu_fragment and pbgpu_segment: the count pass's scratch (result words, one or two row
+    // sums, K and H per source frame), the map (one entry per output record) and segment's slice
+    // sums of the output records, each grown on demand.  The two calls share them: every call that
+    // queues work on them synchronises the stream before it returns, so none finds them in use.
+    // The two count layouts differ, hence that capacity in bytes.
+    uint8_t *d_cut_cnt = nullptr;
+    uint64_t cut_cnt_cap = 0; // bytes
+    uint64_t *d_cut_map = nullptr;
+    uint64_t cut_map_cap = 0; // output records
+    uint32_t *d_cut_psum = nullptr;
+    uint64_t cut_psum_cap = 0; // output records
     unsigned long long *d_sp_res = nullptr; // pbgpu_stamp: the result words
     unsigned long long *d_xl_res = nullptr; // pbgpu_xlat46: the classify pass's result words
     seq_slot seqs[PB_MAX_SEQUENCES];
@@ -849,16 +848,12 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipHostFree(ctx->h_wres);
     if (ctx->d_vcodes)
         (void)hipFree(ctx->d_vcodes);
-    if (ctx->d_fg_cnt)
-        (void)hipFree(ctx->d_fg_cnt);
-    if (ctx->d_fg_map)
-        (void)hipFree(ctx->d_fg_map);
-    if (ctx->d_sg_cnt)
-        (void)hipFree(ctx->d_sg_cnt);
-    if (ctx->d_sg_map)
-        (void)hipFree(ctx->d_sg_map);
-    if (ctx->d_sg_psum)
-        (void)hipFree(ctx->d_sg_psum);
+    if (ctx->d_cut_cnt)
+        (void)hipFree(ctx->d_cut_cnt);
+    if (ctx->d_cut_map)
+        (void)hipFree(ctx->d_cut_map);
+    if (ctx->d_cut_psum)
+        (void)hipFree(ctx->d_cut_psum);
     if (ctx->d_sp_res)
         (void)hipFree(ctx->d_sp_res);
     if (ctx->d_xl_res)
@@ -1864,6 +1859,28 @@ int pbgpu_page_grid(pbgpu_ctx *ctx, uint64_t npages, uint32_t *per, uint32_t *gr
     return page_grid(npages, ctx->opt.rp_per, per, grid);
 }
 
+// The device computes (first_index + j) * step_ps and t0_ns + that / 1000 for j < n in 64 bits:
+// whether the last of them fits
+static bool stamps_fit(uint64_t first_index, uint64_t n, uint64_t step_ps, uint64_t t0_ns)
+{
+    if (n == 0)
+        return true;
+    if (first_index > UINT64_MAX - (n - 1))
+        return false;
+    const uint64_t last = first_index + (n - 1);
+    if (step_ps && last > UINT64_MAX / step_ps)
+        return false;
+    return last * step_ps / 1000u <= UINT64_MAX - t0_ns;
+}
+
+// A byte template as little-endian dwords
+static void pack_le32(uint32_t *dw, const uint8_t *t, uint32_t ndw)
+{
+    for (uint32_t i = 0; i < ndw; ++i)
+        dw[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
+                ((uint32_t)t[4 * i + 3] << 24);
+}
+
 // Frames [first, first + n) of a buffer that holds frames (reserved: set by the first build or upload)
 static bool frames_range_ok(const pbgpu_frames *f, uint64_t first, uint64_t n)
 {
@@ -2760,17 +2777,8 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
         return PBGPU_EINVAL;
     if (opts->flags & ~PB_PCAP_FLAGS)
         return PBGPU_EINVAL;
-    if (n)
-    {
-        // the device computes (first_index + j) * step_ps and t0_ns + that / 1000 in 64 bits
-        if (opts->first_index > UINT64_MAX - (n - 1))
-            return PBGPU_EINVAL;
-        const uint64_t last = opts->first_index + (n - 1);
-        if (opts->step_ps && last > UINT64_MAX / opts->step_ps)
-            return PBGPU_EINVAL;
-        if (last * opts->step_ps / 1000u > UINT64_MAX - opts->t0_ns)
-            return PBGPU_EINVAL;
-    }
+    if (!stamps_fit(opts->first_index, n, opts->step_ps, opts->t0_ns))
+        return PBGPU_EINVAL;
     uint64_t body = 0, src_end = 0;
     PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
     if (src_end > src->capacity_bytes)
@@ -2931,9 +2939,7 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
                 t[38] = (uint8_t)(ulen >> 8), t[39] = (uint8_t)ulen;
             }
         }
-        for (uint32_t i = 0; i < PB_EN_TDW; ++i)
-            A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
-                       ((uint32_t)t[4 * i + 3] << 24);
+        pack_le32(A.tpl, t, PB_EN_TDW);
         uint32_t grid = 0;
         PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
         timing_pair tp;
@@ -2951,16 +2957,47 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
     return mark_built(ctx, dst, st);
 }
 
-// ---- IPv4 fragmentation (DESIGN.md 5.11) ----
+// ---- cutting frames into pieces: IPv4 fragmentation and L4 segmentation ----
 
-// Argument checks shared by the three calls; nothing on the device.
-static int frag_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts)
+struct cut_call;
+
+// What differs between the two calls, for the helpers they share
+struct cut_kind
 {
-    if (ctx == NULL || src == NULL || opts == NULL)
-        return PBGPU_EINVAL;
-    if (opts->mtu < 68u || opts->mtu > 65535u || (opts->flags & ~PBGPU_FRAG_IGNORE_DF) || opts->reserved != 0)
-        return PBGPU_EINVAL;
-    if (!frames_range_ok(src, first, n))
+    uint32_t hdr;     // the fixed L2/L3/L4 header bytes in front of the cut data
+    uint32_t worst;   // the longest inserted header
+    int ins_word;     // the result word holding the inserted bytes; below 0: 34 (n_out - n)
+    uint32_t row_sums; // row sums of the count pass: K, and the inserted bytes where they are counted
+    // stage 0: count and scans; stage 1: map and writer (pbk_launch_frag, pbk_launch_seg)
+    hipError_t (*launch)(const pb_cutargs *A, int stage, int G, uint32_t grid, hipStream_t st);
+    // the kind's own refusals, scratch and arguments of the writer, before dst is touched (may be null)
+    int (*prepare)(pbgpu_ctx *ctx, pb_cutargs *A, const cut_call &c, const unsigned long long *r, uint64_t src_end,
+                   int *G);
+};
+
+// One call's options, checked
+struct cut_call
+{
+    const cut_kind *kd;
+    uint32_t cut;   // data bytes of a full piece: C, or mss
+    uint32_t fit;   // the longest frame that never splits
+    uint32_t flags; // PB_FG_* or PB_SG_*
+    uint32_t mtu;   // fragment
+};
+
+// What the main call's shared body leaves for the result struct
+struct cut_done
+{
+    unsigned long long r[PB_FG_RES_DW];
+    uint64_t n_out, total;
+    const frames_events *fe; // dst's
+    float ms;
+};
+
+// Argument checks shared by all six calls, after the options'; nothing on the device.
+static int cut_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n)
+{
+    if (ctx == NULL || src == NULL || !frames_range_ok(src, first, n))
         return PBGPU_EINVAL;
     const frames_events *fs = (const frames_events *)src->reserved;
     if (src->n_frames && fs->min_len < 14u)
@@ -2968,7 +3005,7 @@ static int frag_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_
     return PBGPU_OK;
 }
 
-static void frag_args(pb_fgargs *A, const pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts)
+static void cut_args(pb_cutargs *A, const pbgpu_frames *src, uint64_t first, uint64_t n, const cut_call &c)
 {
     memset(A, 0, sizeof *A);
     A->src = src->data;
@@ -2976,344 +3013,284 @@ static void frag_args(pb_fgargs *A, const pbgpu_frames *src, uint64_t first, uin
     A->first = first;
     A->n = n;
     A->fixed_len = src->fixed_len;
-    A->mtu = opts->mtu;
-    A->C = (opts->mtu - 20u) & ~7u;
-    A->cdiv = make_div(A->C);
-    A->flags = (opts->flags & PBGPU_FRAG_IGNORE_DF) ? PB_FG_IGNORE_DF : 0u;
+    A->cut = c.cut;
+    A->cdiv = make_div(c.cut);
+    A->mtu = c.mtu;
+    A->flags = c.flags;
 }
 
 // The count and scan stages, queued on the context's stream: A's scratch pointers are set, the
 // result words arrive in res[] with the stream's next synchronise.
-static int frag_count(pbgpu_ctx *ctx, pb_fgargs *A, unsigned long long *res)
+static int cut_count(pbgpu_ctx *ctx, pb_cutargs *A, const cut_call &c, unsigned long long *res)
 {
     const uint64_t nblk = (A->n + PB_FG_WT - 1u) / PB_FG_WT;
     if (nblk > 0xFFFFFFFFull)
         return PBGPU_EINVAL;
-    PBCHK(scratch_reserve((void **)&ctx->d_fg_cnt, &ctx->fg_cnt_cap, A->n, PB_FG_RES_DW * 8u + nblk * 8u + A->n * 4u));
-    A->res = (unsigned long long *)ctx->d_fg_cnt;
+    const uint64_t bytes = PB_FG_RES_DW * 8u + nblk * 8u * c.kd->row_sums + A->n * 4u;
+    PBCHK(scratch_reserve((void **)&ctx->d_cut_cnt, &ctx->cut_cnt_cap, bytes, bytes));
+    A->res = (unsigned long long *)ctx->d_cut_cnt;
     A->bsum = A->res + PB_FG_RES_DW;
-    A->kcnt = (uint32_t *)(A->bsum + nblk);
-    HIPCHK(pbk_launch_frag(A, 0, 0, ctx->stream));
+    A->xsum = c.kd->row_sums > 1u ? A->bsum + nblk : nullptr;
+    A->kcnt = (uint32_t *)(A->bsum + nblk * c.kd->row_sums);
+    HIPCHK(c.kd->launch(A, 0, 0, 0, ctx->stream));
     HIPCHK(hipMemcpyAsync(res, A->res, PB_FG_RES_DW * 8u, hipMemcpyDeviceToHost, ctx->stream));
     return PBGPU_OK;
+}
+
+// the bytes that n_out = r[0] output records of n source frames have had inserted
+static uint64_t cut_inserted(const cut_call &c, const unsigned long long *r, uint64_t n)
+{
+    return c.kd->ins_word < 0 ? 34u * (r[0] - n) : r[c.kd->ins_word];
+}
+
+static int cut_bound(const pbgpu_frames *src, uint64_t n, const cut_call &c, uint64_t *frames, uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const uint64_t max_len = fs->max_len;
+    uint64_t kmax = 1;
+    if (max_len > c.fit)
+        kmax = (max_len - c.kd->hdr + c.cut - 1u) / c.cut;
+    *frames = n * kmax;
+    *bytes = n * (src->fixed_len ? src->fixed_len : max_len) + (uint64_t)c.kd->worst * n * (kmax - 1u);
+    return PBGPU_OK;
+}
+
+static int cut_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const cut_call &c, uint64_t *frames,
+                    uint64_t *bytes)
+{
+    if (frames == NULL || bytes == NULL)
+        return PBGPU_EINVAL;
+    uint64_t body = 0, src_end = 0;
+    PBCHK(range_bytes(ctx, src, first, n, &body, &src_end));
+    *frames = n;
+    *bytes = body;
+    const frames_events *fs = (const frames_events *)src->reserved;
+    if (n == 0 || fs->max_len <= c.fit) // nothing can split
+        return PBGPU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    pb_cutargs A;
+    cut_args(&A, src, first, n, c);
+    unsigned long long r[PB_FG_RES_DW];
+    PBCHK(cut_count(ctx, &A, c, r));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (r[0] < n)
+        return PBGPU_EIO;
+    *frames = r[0];
+    *bytes = body + cut_inserted(c, r, n);
+    return PBGPU_OK;
+}
+
+// The main call up to, and without, mark_built: the caller fills its result struct from d first.
+static int cut_run(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const cut_call &c, pbgpu_frames *dst,
+                   cut_done *d)
+{
+    if (dst == NULL || src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+        return PBGPU_EINVAL;
+    uint64_t body = 0, src_end = 0;
+    PBCHK(range_bytes(ctx, src, first, n, &body, &src_end));
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    hipStream_t st = ctx->stream;
+    // a fixed-length source none of whose frames can split: no count, a plain copy
+    const bool copy = src->fixed_len && src->fixed_len <= c.fit;
+    pb_cutargs A;
+    cut_args(&A, src, first, n, c);
+    const unsigned long long r0[PB_FG_RES_DW] = {n, 0, 0, 0, src->fixed_len, src->fixed_len, 0, 0};
+    unsigned long long *r = d->r;
+    memcpy(r, r0, sizeof r0);
+    timing_pair tp = {nullptr, nullptr};
+    if (n)
+    {
+        PBCHK(timed_begin(ctx, &tp)); // the timed stretch: count, scans, map, segment's sums and writer
+        if (!copy)
+        {
+            // the count and scans run, and their result is read, before anything of dst is touched
+            PBCHK(cut_count(ctx, &A, c, r));
+            HIPCHK(hipStreamSynchronize(st));
+            if (r[0] < n)
+                return PBGPU_EIO;
+        }
+    }
+    const uint64_t n_out = r[0];
+    const uint64_t total = body + cut_inserted(c, r, n);
+    const uint64_t end16 = (total + 15) & ~15ull;
+    if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    int G = 0;
+    if (n && !copy)
+    {
+        A.n_out = n_out;
+        if (c.kd->prepare)
+            PBCHK(c.kd->prepare(ctx, &A, c, r, src_end, &G));
+        PBCHK(scratch_reserve((void **)&ctx->d_cut_map, &ctx->cut_map_cap, n_out, n_out * sizeof(uint64_t)));
+    }
+    frames_events *fe = nullptr;
+    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, &fe));
+    d->ms = 0;
+    if (n)
+    {
+        uint32_t grid = 0;
+        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
+        if (copy)
+            HIPCHK(pbk_launch_cut_copy(src->data, dst->data, first * src->fixed_len, total, end16, A.per, grid, st));
+        else
+        {
+            A.dst = dst->data;
+            A.dst_offsets = dst->offsets;
+            A.map = ctx->d_cut_map;
+            A.total = total;
+            A.end16 = end16;
+            HIPCHK(c.kd->launch(&A, 1, G, grid, st));
+        }
+        PBCHK(timed_stop(ctx, tp));
+        PBCHK(timed_ms(ctx, tp, &d->ms));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = n_out;
+    dst->fixed_len = (n && copy) ? src->fixed_len : 0;
+    dst->total_bytes = total;
+    d->n_out = n_out;
+    d->total = total;
+    d->fe = fe;
+    return PBGPU_OK;
+}
+
+// ---- IPv4 fragmentation (DESIGN.md 5.11) ----
+
+static hipError_t frag_launch(const pb_cutargs *A, int stage, int, uint32_t grid, hipStream_t st)
+{
+    return pbk_launch_frag(A, stage, grid, st);
+}
+
+static const cut_kind FRAG_KIND = {34u, 34u, -1, 1u, frag_launch, nullptr};
+
+static int frag_call(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_frag_opts *opts,
+                     cut_call *c)
+{
+    if (opts == NULL)
+        return PBGPU_EINVAL;
+    if (opts->mtu < 68u || opts->mtu > 65535u || (opts->flags & ~PBGPU_FRAG_IGNORE_DF) || opts->reserved != 0)
+        return PBGPU_EINVAL;
+    *c = {&FRAG_KIND, (opts->mtu - 20u) & ~7u, opts->mtu + 14u,
+          (opts->flags & PBGPU_FRAG_IGNORE_DF) ? PB_FG_IGNORE_DF : 0u, opts->mtu};
+    return cut_check(ctx, src, first, n);
 }
 
 int pbgpu_fragment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                          const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes)
 {
-    if (frames == NULL || bytes == NULL)
-        return PBGPU_EINVAL;
-    PBCHK(frag_check(ctx, src, first_frame, n, opts));
-    const frames_events *fs = (const frames_events *)src->reserved;
-    const uint64_t C = (opts->mtu - 20u) & ~7u, max_len = fs->max_len;
-    uint64_t kmax = 1;
-    if (max_len > opts->mtu + 14ull)
-        kmax = (max_len - 34u + C - 1u) / C;
-    *frames = n * kmax;
-    *bytes = n * (src->fixed_len ? src->fixed_len : max_len) + 34u * n * (kmax - 1u);
-    return PBGPU_OK;
+    cut_call c;
+    PBCHK(frag_call(ctx, src, first_frame, n, opts, &c));
+    return cut_bound(src, n, c, frames, bytes);
 }
 
 int pbgpu_fragment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                         const pbgpu_frag_opts *opts, uint64_t *frames, uint64_t *bytes)
 {
-    if (frames == NULL || bytes == NULL)
-        return PBGPU_EINVAL;
-    PBCHK(frag_check(ctx, src, first_frame, n, opts));
-    uint64_t body = 0, src_end = 0;
-    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
-    *frames = n;
-    *bytes = body;
-    const frames_events *fs = (const frames_events *)src->reserved;
-    if (n == 0 || fs->max_len <= opts->mtu + 14u) // nothing can split
-        return PBGPU_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    pb_fgargs A;
-    frag_args(&A, src, first_frame, n, opts);
-    unsigned long long r[PB_FG_RES_DW];
-    PBCHK(frag_count(ctx, &A, r));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (r[0] < n)
-        return PBGPU_EIO;
-    *frames = r[0];
-    *bytes = body + 34u * (r[0] - n);
-    return PBGPU_OK;
+    cut_call c;
+    PBCHK(frag_call(ctx, src, first_frame, n, opts, &c));
+    return cut_size(ctx, src, first_frame, n, c, frames, bytes);
 }
 
 int pbgpu_fragment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_frag_opts *opts,
                    pbgpu_frames *dst, pbgpu_frag_result *res)
 {
-    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
-        return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
-        return PBGPU_EINVAL;
-    PBCHK(frag_check(ctx, src, first_frame, n, opts));
-    uint64_t body = 0, src_end = 0;
-    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
-    if (src_end > src->capacity_bytes)
-        return PBGPU_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    hipStream_t st = ctx->stream;
-    // a fixed-length source none of whose frames can split: no count, a plain copy
-    const bool copy = src->fixed_len && src->fixed_len <= opts->mtu + 14u;
-    pb_fgargs A;
-    frag_args(&A, src, first_frame, n, opts);
-    unsigned long long r[PB_FG_RES_DW] = {n, 0, 0, 0, src->fixed_len, src->fixed_len, 0, 0};
-    timing_pair tp = {nullptr, nullptr};
-    if (n)
-    {
-        PBCHK(timed_begin(ctx, &tp)); // the timed stretch: count, scan, map and writer
-        if (!copy)
-        {
-            // the count and scan run, and their result is read, before anything of dst is touched
-            PBCHK(frag_count(ctx, &A, r));
-            HIPCHK(hipStreamSynchronize(st));
-            if (r[0] < n)
-                return PBGPU_EIO;
-        }
-    }
-    const uint64_t n_out = n ? r[0] : 0;
-    const uint64_t total = body + 34u * (n_out - n);
-    const uint64_t end16 = (total + 15) & ~15ull;
-    if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
-        return PBGPU_ENOSPC;
-    if (n && !copy)
-        PBCHK(scratch_reserve((void **)&ctx->d_fg_map, &ctx->fg_map_cap, n_out, n_out * sizeof(uint64_t)));
-    frames_events *fe = nullptr;
-    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, &fe));
-    float ms = 0;
-    if (n)
-    {
-        A.dst = dst->data;
-        A.dst_offsets = dst->offsets;
-        A.map = ctx->d_fg_map;
-        A.n_out = n_out;
-        A.total = total;
-        A.end16 = end16;
-        uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
-        HIPCHK(pbk_launch_frag(&A, copy ? 2 : 1, grid, st));
-        PBCHK(timed_stop(ctx, tp));
-        PBCHK(timed_ms(ctx, tp, &ms));
-    }
-    dst->first_iter = 0;
-    dst->n_frames = n_out;
-    dst->fixed_len = (n && copy) ? src->fixed_len : 0;
-    dst->total_bytes = total;
+    cut_call c;
+    cut_done d;
+    PBCHK(frag_call(ctx, src, first_frame, n, opts, &c));
+    PBCHK(cut_run(ctx, src, first_frame, n, c, dst, &d));
     if (res)
     {
         memset(res, 0, sizeof *res);
         res->n_in = n;
-        res->n_out = n_out;
-        res->n_split = n ? r[1] : 0;
-        res->n_df = n ? r[2] : 0;
-        res->n_other = n ? r[3] : 0;
-        res->out_bytes = total;
-        res->out_min_len = fe->min_len;
-        res->out_max_len = fe->max_len;
-        res->device_ms = ms;
+        res->n_out = d.n_out;
+        res->n_split = d.r[1];
+        res->n_df = d.r[2];
+        res->n_other = d.r[3];
+        res->out_bytes = d.total;
+        res->out_min_len = d.fe->min_len;
+        res->out_max_len = d.fe->max_len;
+        res->device_ms = d.ms;
     }
-    return mark_built(ctx, dst, st);
+    return mark_built(ctx, dst, ctx->stream);
 }
 
 // ---- L4 segmentation ----
 
-// Argument checks shared by the three calls; nothing on the device.
-static int seg_check(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_seg_opts *opts)
+static int seg_prepare(pbgpu_ctx *ctx, pb_cutargs *A, const cut_call &c, const unsigned long long *r, uint64_t src_end,
+                       int *G)
 {
-    if (ctx == NULL || src == NULL || opts == NULL)
+    if (src_end >> PB_SG_M_ISH) // a map entry keeps 44 bits of source offset
+        return PBGPU_EINVAL;
+    const bool sums = !(c.flags & PB_SG_NO_L4);
+    if (sums)
+        PBCHK(scratch_reserve((void **)&ctx->d_cut_psum, &ctx->cut_psum_cap, A->n_out, A->n_out * sizeof(uint32_t)));
+    A->psum = ctx->d_cut_psum;
+    A->hdw = 10u + (uint32_t)(r[7] < 15u ? r[7] : 15u);
+    // lanes per segment by the slice length, as verify_shape picks pb_vst_kernel's G
+    *G = !sums ? 0 : c.cut <= 256u ? 8 : c.cut <= 512u ? 16 : c.cut <= 2048u ? 32 : 64;
+    return PBGPU_OK;
+}
+
+static const cut_kind SEG_KIND = {42u, 94u, 6, 2u, pbk_launch_seg, seg_prepare};
+
+static int seg_call(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_seg_opts *opts,
+                    cut_call *c)
+{
+    if (opts == NULL)
         return PBGPU_EINVAL;
     if (opts->mss < 8u || opts->mss > 65535u || (opts->flags & ~(PBGPU_SEG_NO_L4_CSUM | PBGPU_SEG_FIXED_ID)) ||
         opts->reserved != 0)
         return PBGPU_EINVAL;
-    if (!frames_range_ok(src, first, n))
-        return PBGPU_EINVAL;
-    const frames_events *fs = (const frames_events *)src->reserved;
-    if (src->n_frames && fs->min_len < 14u)
-        return PBGPU_EINVAL;
-    return PBGPU_OK;
-}
-
-static void seg_args(pb_sgargs *A, const pbgpu_frames *src, uint64_t first, uint64_t n, const pbgpu_seg_opts *opts)
-{
-    memset(A, 0, sizeof *A);
-    A->src = src->data;
-    A->offsets = src->fixed_len ? nullptr : src->offsets;
-    A->first = first;
-    A->n = n;
-    A->fixed_len = src->fixed_len;
-    A->mss = opts->mss;
-    A->mdiv = make_div(opts->mss);
-    A->flags = ((opts->flags & PBGPU_SEG_NO_L4_CSUM) ? PB_SG_NO_L4 : 0u) |
-               ((opts->flags & PBGPU_SEG_FIXED_ID) ? PB_SG_FIXED_ID : 0u);
-}
-
-// The count and the two scans, queued on the context's stream: A's scratch pointers are set, the
-// result words arrive in res[] with the stream's next synchronise.
-static int seg_count(pbgpu_ctx *ctx, pb_sgargs *A, unsigned long long *res)
-{
-    const uint64_t nblk = (A->n + PB_FG_WT - 1u) / PB_FG_WT;
-    if (nblk > 0xFFFFFFFFull)
-        return PBGPU_EINVAL;
-    PBCHK(scratch_reserve((void **)&ctx->d_sg_cnt, &ctx->sg_cnt_cap, A->n, PB_SG_RES_DW * 8u + nblk * 16u + A->n * 4u));
-    A->res = (unsigned long long *)ctx->d_sg_cnt;
-    A->bsum = A->res + PB_SG_RES_DW;
-    A->xsum = A->bsum + nblk;
-    A->kcnt = (uint32_t *)(A->xsum + nblk);
-    HIPCHK(pbk_launch_seg(A, 0, 0, 0, ctx->stream));
-    HIPCHK(hipMemcpyAsync(res, A->res, PB_SG_RES_DW * 8u, hipMemcpyDeviceToHost, ctx->stream));
-    return PBGPU_OK;
+    *c = {&SEG_KIND, opts->mss, opts->mss + 42u,
+          ((opts->flags & PBGPU_SEG_NO_L4_CSUM) ? PB_SG_NO_L4 : 0u) |
+              ((opts->flags & PBGPU_SEG_FIXED_ID) ? PB_SG_FIXED_ID : 0u),
+          0u};
+    return cut_check(ctx, src, first, n);
 }
 
 int pbgpu_segment_bound(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                         const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes)
 {
-    if (frames == NULL || bytes == NULL)
-        return PBGPU_EINVAL;
-    PBCHK(seg_check(ctx, src, first_frame, n, opts));
-    const frames_events *fs = (const frames_events *)src->reserved;
-    const uint64_t mss = opts->mss, max_len = fs->max_len;
-    uint64_t kmax = 1;
-    if (max_len > mss + 42ull)
-        kmax = (max_len - 42u + mss - 1u) / mss;
-    *frames = n * kmax;
-    *bytes = n * (src->fixed_len ? src->fixed_len : max_len) + 94u * n * (kmax - 1u);
-    return PBGPU_OK;
+    cut_call c;
+    PBCHK(seg_call(ctx, src, first_frame, n, opts, &c));
+    return cut_bound(src, n, c, frames, bytes);
 }
 
 int pbgpu_segment_size(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n,
                        const pbgpu_seg_opts *opts, uint64_t *frames, uint64_t *bytes)
 {
-    if (frames == NULL || bytes == NULL)
-        return PBGPU_EINVAL;
-    PBCHK(seg_check(ctx, src, first_frame, n, opts));
-    uint64_t body = 0, src_end = 0;
-    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
-    *frames = n;
-    *bytes = body;
-    const frames_events *fs = (const frames_events *)src->reserved;
-    if (n == 0 || fs->max_len <= opts->mss + 42u) // nothing can split
-        return PBGPU_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    pb_sgargs A;
-    seg_args(&A, src, first_frame, n, opts);
-    unsigned long long r[PB_SG_RES_DW];
-    PBCHK(seg_count(ctx, &A, r));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (r[0] < n)
-        return PBGPU_EIO;
-    *frames = r[0];
-    *bytes = body + r[6];
-    return PBGPU_OK;
+    cut_call c;
+    PBCHK(seg_call(ctx, src, first_frame, n, opts, &c));
+    return cut_size(ctx, src, first_frame, n, c, frames, bytes);
 }
 
 int pbgpu_segment(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_t n, const pbgpu_seg_opts *opts,
                   pbgpu_frames *dst, pbgpu_seg_result *res)
 {
-    if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
-        return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
-        return PBGPU_EINVAL;
-    PBCHK(seg_check(ctx, src, first_frame, n, opts));
-    uint64_t body = 0, src_end = 0;
-    PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
-    if (src_end > src->capacity_bytes)
-        return PBGPU_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    hipStream_t st = ctx->stream;
-    // a fixed-length source none of whose frames can split: no count, a plain copy
-    const bool copy = src->fixed_len && src->fixed_len <= opts->mss + 42u;
-    pb_sgargs A;
-    seg_args(&A, src, first_frame, n, opts);
-    unsigned long long r[PB_SG_RES_DW] = {n, 0, 0, 0, src->fixed_len, src->fixed_len, 0, 0};
-    timing_pair tp = {nullptr, nullptr};
-    if (n)
-    {
-        PBCHK(timed_begin(ctx, &tp)); // the timed stretch: count, scans, map, sums and writer
-        if (!copy)
-        {
-            // the count and scans run, and their result is read, before anything of dst is touched
-            PBCHK(seg_count(ctx, &A, r));
-            HIPCHK(hipStreamSynchronize(st));
-            if (r[0] < n)
-                return PBGPU_EIO;
-        }
-    }
-    const uint64_t n_out = n ? r[0] : 0;
-    const uint64_t total = body + (n ? r[6] : 0);
-    const uint64_t end16 = (total + 15) & ~15ull;
-    if (n_out > dst->capacity_frames || end16 > dst->capacity_bytes)
-        return PBGPU_ENOSPC;
-    const bool sums = !(opts->flags & PBGPU_SEG_NO_L4_CSUM);
-    if (n && !copy)
-    {
-        if (src_end >> PB_SG_M_ISH) // a map entry keeps 44 bits of source offset
-            return PBGPU_EINVAL;
-        PBCHK(scratch_reserve((void **)&ctx->d_sg_map, &ctx->sg_map_cap, n_out, n_out * sizeof(uint64_t)));
-        if (sums)
-            PBCHK(scratch_reserve((void **)&ctx->d_sg_psum, &ctx->sg_psum_cap, n_out, n_out * sizeof(uint32_t)));
-    }
-    frames_events *fe = nullptr;
-    PBCHK(take_dst(dst, st, n ? (uint32_t)r[4] : 0, n ? (uint32_t)r[5] : 0, &fe));
-    float ms = 0;
-    if (n)
-    {
-        uint32_t grid = 0, per = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &per, &grid));
-        if (copy)
-        {
-            pb_fgargs F;
-            memset(&F, 0, sizeof F);
-            F.src = src->data;
-            F.dst = dst->data;
-            F.first = first_frame;
-            F.n = n;
-            F.fixed_len = src->fixed_len;
-            F.total = total;
-            F.end16 = end16;
-            F.per = per;
-            HIPCHK(pbk_launch_frag(&F, 2, grid, st));
-        }
-        else
-        {
-            A.dst = dst->data;
-            A.dst_offsets = dst->offsets;
-            A.map = ctx->d_sg_map;
-            A.psum = ctx->d_sg_psum;
-            A.n_out = n_out;
-            A.total = total;
-            A.end16 = end16;
-            A.per = per;
-            A.hdw = 10u + (uint32_t)(r[7] < 15u ? r[7] : 15u);
-            // lanes per segment by the slice length, as verify_shape picks pb_vst_kernel's G
-            const int G = !sums ? 0 : opts->mss <= 256u ? 8 : opts->mss <= 512u ? 16 : opts->mss <= 2048u ? 32 : 64;
-            HIPCHK(pbk_launch_seg(&A, 1, G, grid, st));
-        }
-        PBCHK(timed_stop(ctx, tp));
-        PBCHK(timed_ms(ctx, tp, &ms));
-    }
-    dst->first_iter = 0;
-    dst->n_frames = n_out;
-    dst->fixed_len = (n && copy) ? src->fixed_len : 0;
-    dst->total_bytes = total;
+    cut_call c;
+    cut_done d;
+    PBCHK(seg_call(ctx, src, first_frame, n, opts, &c));
+    PBCHK(cut_run(ctx, src, first_frame, n, c, dst, &d));
     if (res)
     {
         memset(res, 0, sizeof *res);
         res->n_in = n;
-        res->n_out = n_out;
-        res->n_split_tcp = n ? r[1] : 0;
-        res->n_split_udp = n ? r[2] : 0;
-        res->n_other = n ? r[3] : 0;
-        res->out_bytes = total;
-        res->out_min_len = fe->min_len;
-        res->out_max_len = fe->max_len;
-        res->device_ms = ms;
+        res->n_out = d.n_out;
+        res->n_split_tcp = d.r[1];
+        res->n_split_udp = d.r[2];
+        res->n_other = d.r[3];
+        res->out_bytes = d.total;
+        res->out_min_len = d.fe->min_len;
+        res->out_max_len = d.fe->max_len;
+        res->device_ms = d.ms;
     }
-    return mark_built(ctx, dst, st);
+    return mark_built(ctx, dst, ctx->stream);
 }
 
 // ---- stamping ----
@@ -3325,17 +3302,8 @@ int pbgpu_stamp(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t 
         return PBGPU_EINVAL;
     if ((opts->flags & ~(PBGPU_STAMP_TAIL | PBGPU_STAMP_NO_CSUM)) || opts->offset > 65535u)
         return PBGPU_EINVAL;
-    if (n)
-    {
-        // as pbgpu_pcap_pack: the device computes the index, its product and the timestamp in 64 bits
-        if (opts->first_index > UINT64_MAX - (n - 1))
-            return PBGPU_EINVAL;
-        const uint64_t last = opts->first_index + (n - 1);
-        if (opts->step_ps && last > UINT64_MAX / opts->step_ps)
-            return PBGPU_EINVAL;
-        if (last * opts->step_ps / 1000u > UINT64_MAX - opts->t0_ns)
-            return PBGPU_EINVAL;
-    }
+    if (!stamps_fit(opts->first_index, n, opts->step_ps, opts->t0_ns))
+        return PBGPU_EINVAL;
     uint64_t body = 0, end = 0;
     PBCHK(range_bytes(ctx, f, first_frame, n, &body, &end)); // the range check; variable length: offsets[] in place
     if (end > f->capacity_bytes)
@@ -3469,9 +3437,7 @@ int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64
             A.ksum += ((uint32_t)t[i] << 8) | t[i + 1];
         while (A.ksum >> 16)
             A.ksum = (A.ksum & 0xFFFFu) + (A.ksum >> 16);
-        for (uint32_t i = 0; i < 8; ++i)
-            A.tpl[i] = (uint32_t)t[4 * i] | ((uint32_t)t[4 * i + 1] << 8) | ((uint32_t)t[4 * i + 2] << 16) |
-                       ((uint32_t)t[4 * i + 3] << 24);
+        pack_le32(A.tpl, t, 8);
         // the timed stretch: classify and writer; the classify result is read before anything of dst is touched
         PBCHK(timed_begin(ctx, &tp));
         HIPCHK(pbk_launch_xlat(&A, 0, 0, st));

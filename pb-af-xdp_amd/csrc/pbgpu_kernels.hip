@@ -4849,6 +4849,27 @@ __device__ __forceinline__ void pb_rp_next_page(int32_t &d0, uint64_t &j0, const
     j0 += kn;
 }
 
+// Frame first + j of a range: its first byte o in the buffer and its length L, from offsets[]
+// (var) or the fixed length; with ob, also the range's first byte
+__device__ __forceinline__ void pb_rp_frame(const uint64_t *offsets, uint64_t first, uint32_t fixed_len, bool var,
+                                            uint64_t j, uint64_t &o, uint32_t &L, uint64_t *ob = nullptr)
+{
+    if (var)
+    {
+        if (ob)
+            *ob = offsets[first];
+        o = offsets[first + j];
+        L = (uint32_t)(offsets[first + j + 1] - o);
+    }
+    else
+    {
+        if (ob)
+            *ob = first * fixed_len;
+        o = (first + j) * fixed_len;
+        L = fixed_len;
+    }
+}
+
 // ---------------- pcap stream packing (pbgpu_pcap_pack) ----------------
 // The stream: the 24-B pcap file header (optional), then per frame a 16-B record header
 // {ts_sec, ts_frac, len, len} and the frame's bytes.  Destination-owned: a workgroup owns `per`
@@ -5297,123 +5318,147 @@ extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStr
     return hipGetLastError();
 }
 
-// ---------------- IPv4 fragmentation (pbgpu_fragment, DESIGN.md 5.11) ----------------
-// The output is the source byte stream with a 34-B header inserted before every fragment i >= 1
-// and three fields patched in every fragment's header; everything else sits at its source position
-// plus 34 times the number of insertions before it.  The output frame count depends on the data,
-// so three stages: count (K per source frame, their sums per workgroup, the result counts), scan
-// (pb_scan_blocks over the workgroup sums; pb_frag_map_kernel then writes dst->offsets and one map
-// entry per output record) and the destination-owned writer.
+// ---------------- cutting frames into pieces: the scaffold of fragment and segment ----------------
+// Both calls cut the data of a source frame into K pieces of at most A.cut bytes and put the frame's
+// own header, patched, before every piece: the output is the source byte stream with a header
+// inserted before every piece i >= 1 and some fields patched in every piece's header; everything
+// else sits at its source position plus the inserted bytes before it.  The output frame count
+// depends on the data, so three stages: count (K per source frame, their sums per row of PB_FG_WT
+// frames, the result counts), scan (pb_scan_blocks over the row sums; the map kernel then writes
+// dst->offsets and one map entry per output record) and the destination-owned writer.
+//
+// The stages exist once, as templates over a kind (pb_fg_kind, pb_sg_kind below), which supplies
+//   VARH                the inserted header's length differs from frame to frame: H / 4 rides in
+//                       kcnt[] and the map entry, and the inserted bytes get a row sum and a scan
+//                       of their own (else every inserted header is 34 B and 34 (F(j) - j) does)
+//   ISH, PIECE, IMASK   the map entry's shift, its "is a piece" bit and the piece index's mask
+//   bits()              the map bits of piece i
+//   hlen(), hdw()       the header's length by the map bits, the dwords of a staged header slot
+//   classify()          count: K, the inserted bytes, H / 4 and the output lengths of one frame
+//   header()            writer: the piece's header, read from the source and patched, into T[]
 
-__global__ __launch_bounds__(64) void pb_frag_init_kernel(unsigned long long *res)
+// what the count pass learns of one source frame: pieces, inserted bytes, H / 4 (VARH), and its
+// shortest and longest output record
+struct pb_cut_frame
+{
+    uint32_t K, X, hq, lmin, lmax;
+};
+
+// bytes 12..15 and 20..23 of the frame at o, from aligned dwords inside it (it is longer than 28 B)
+__device__ __forceinline__ void pb_cut_read12(const uint32_t *w, uint64_t o, uint32_t &b12, uint32_t &b20)
+{
+    const uint64_t a = o + 12u, i = a >> 2;
+    const uint32_t sh = (uint32_t)a & 3u;
+    const uint32_t d0 = w[i], d1 = w[i + 1], d2 = w[i + 2], d3 = w[i + 3];
+    b12 = __builtin_amdgcn_alignbyte(d1, d0, sh);
+    b20 = __builtin_amdgcn_alignbyte(d3, d2, sh);
+}
+
+__global__ __launch_bounds__(64) void pb_cut_init_kernel(unsigned long long *res)
 {
     if (threadIdx.x < PB_FG_RES_DW)
         res[threadIdx.x] = threadIdx.x == 4u ? 0xFFFFFFFFull : 0ull;
 }
 
 // Count: one lane per source frame, PB_FG_CB rows of 256 frames per workgroup (one K sum per row for
-// the scan; the result counts are kept in registers across the rows, so the atomics on the six
-// result words come once per 4,096 frames: at one per 256 they were most of this stage's time).
-// A frame that fits (L - 14 <= mtu) is never read; of the others bytes 12..23 come from aligned
-// dwords inside the frame (it is longer than 82 B).
-__global__ __launch_bounds__(PB_FG_WT) void pb_frag_count_kernel(pb_fgargs A)
+// the scan; the result counts are kept in registers across the rows, so the atomics on the result
+// words come once per 4,096 frames: at one per 256 they were most of this stage's time).
+template <class KIND>
+__device__ __forceinline__ void pb_cut_count(const pb_cutargs &A)
 {
-    __shared__ uint32_t s_k[2][PB_FG_WT / 64u];
-    __shared__ uint32_t s_red[5 * (PB_FG_WT / 64u)];
+    constexpr uint32_t NW = PB_FG_WT / 64u, NS = KIND::VARH ? 2u : 1u, NR = KIND::VARH ? 6u : 5u;
+    __shared__ uint32_t s_k[2][NS][NW];
+    __shared__ uint32_t s_red[NR * NW];
     const uint32_t tid = threadIdx.x, wv = tid >> 6;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
     const uint64_t nrow = (A.n + PB_FG_WT - 1u) / PB_FG_WT;
-    uint32_t split = 0, df = 0, other = 0, omin = 0xFFFFFFFFu, omax = 0;
+    uint32_t c[3] = {0, 0, 0}, omin = 0xFFFFFFFFu, omax = 0, hmax = 0;
     for (uint32_t ri = 0; ri < PB_FG_CB; ++ri)
     {
         const uint64_t row = (uint64_t)blockIdx.x * PB_FG_CB + ri;
         if (row >= nrow)
             break;
         const uint64_t j = row * PB_FG_WT + tid;
-        uint32_t K = 0;
+        uint32_t K = 0, X = 0;
         if (j < A.n)
         {
             uint64_t o;
             uint32_t L;
-            if (A.offsets)
-            {
-                o = A.offsets[A.first + j];
-                L = (uint32_t)(A.offsets[A.first + j + 1] - o);
-            }
-            else
-            {
-                o = (A.first + j) * A.fixed_len;
-                L = A.fixed_len;
-            }
-            K = 1;
-            uint32_t lmin = L, lmax = L;
-            if (L > A.mtu + 14u)
-            {
-                const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-                const uint64_t a = o + 12u, i = a >> 2;
-                const uint32_t sh = (uint32_t)a & 3u;
-                const uint32_t d0 = w[i], d1 = w[i + 1], d2 = w[i + 2], d3 = w[i + 3];
-                const uint32_t b12 = __builtin_amdgcn_alignbyte(d1, d0, sh); // bytes 12..15
-                const uint32_t b20 = __builtin_amdgcn_alignbyte(d3, d2, sh); // bytes 20..23
-                const uint32_t fo = pb_bswap16(b20 & 0xFFFFu);
-                if ((b12 & 0x00FFFFFFu) != 0x00450008u)
-                    other += 1;
-                else if ((fo & 0x4000u) && !(A.flags & PB_FG_IGNORE_DF))
-                    df += 1;
-                else
-                {
-                    const uint32_t D = L - 34u;
-                    K = pb_divq(D + A.C - 1u, A.cdiv);
-                    split += 1;
-                    lmax = 34u + A.C;
-                    lmin = 34u + D - (K - 1u) * A.C;
-                }
-            }
-            omin = lmin < omin ? lmin : omin;
-            omax = lmax > omax ? lmax : omax;
-            A.kcnt[j] = K;
+            pb_rp_frame(A.offsets, A.first, A.fixed_len, A.offsets != nullptr, j, o, L);
+            const pb_cut_frame f = KIND::classify(A, w, o, L, c);
+            K = f.K, X = f.X;
+            omin = f.lmin < omin ? f.lmin : omin;
+            omax = f.lmax > omax ? f.lmax : omax;
+            hmax = f.hq > hmax ? f.hq : hmax;
+            A.kcnt[j] = KIND::VARH ? f.K | f.hq << 16 : f.K;
         }
-        uint32_t sumK = K;
+        uint32_t sumK = K, sumX = X;
 #pragma unroll
         for (uint32_t dd = 32; dd > 0; dd >>= 1)
+        {
             sumK += __shfl_xor(sumK, dd, 64);
-        if ((tid & 63u) == 0)
-            s_k[ri & 1u][wv] = sumK; // two sets: a row's readers and the next row's writers never meet
+            if (KIND::VARH)
+                sumX += __shfl_xor(sumX, dd, 64);
+        }
+        if ((tid & 63u) == 0) // two sets: a row's readers and the next row's writers never meet
+        {
+            s_k[ri & 1u][0][wv] = sumK;
+            if (KIND::VARH)
+                s_k[ri & 1u][NS - 1u][wv] = sumX;
+        }
         __syncthreads();
         if (tid == 0)
         {
-            uint32_t t = 0;
+            uint32_t t = 0, x = 0;
 #pragma unroll
-            for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
-                t += s_k[ri & 1u][v];
+            for (uint32_t v = 0; v < NW; ++v)
+            {
+                t += s_k[ri & 1u][0][v];
+                if (KIND::VARH)
+                    x += s_k[ri & 1u][NS - 1u][v];
+            }
             A.bsum[row] = t;
+            if (KIND::VARH)
+                A.xsum[row] = x;
         }
     }
 #pragma unroll
     for (uint32_t dd = 32; dd > 0; dd >>= 1)
     {
-        split += __shfl_xor(split, dd, 64);
-        df += __shfl_xor(df, dd, 64);
-        other += __shfl_xor(other, dd, 64);
+#pragma unroll
+        for (uint32_t u = 0; u < 3u; ++u)
+            c[u] += __shfl_xor(c[u], dd, 64);
         const uint32_t mn = __shfl_xor(omin, dd, 64), mx = __shfl_xor(omax, dd, 64);
         omin = mn < omin ? mn : omin;
         omax = mx > omax ? mx : omax;
+        if (KIND::VARH)
+        {
+            const uint32_t hx = __shfl_xor(hmax, dd, 64);
+            hmax = hx > hmax ? hx : hmax;
+        }
     }
     if ((tid & 63u) == 0)
     {
-        s_red[5 * wv + 0] = split, s_red[5 * wv + 1] = df, s_red[5 * wv + 2] = other;
-        s_red[5 * wv + 3] = omin, s_red[5 * wv + 4] = omax;
+        s_red[NR * wv + 0] = c[0], s_red[NR * wv + 1] = c[1], s_red[NR * wv + 2] = c[2];
+        s_red[NR * wv + 3] = omin, s_red[NR * wv + 4] = omax;
+        if (KIND::VARH)
+            s_red[NR * wv + NR - 1u] = hmax;
     }
     __syncthreads();
     if (tid == 0)
     {
-        uint32_t r[5] = {0, 0, 0, 0xFFFFFFFFu, 0};
+        uint32_t r[6] = {0, 0, 0, 0xFFFFFFFFu, 0, 0};
 #pragma unroll
-        for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
+        for (uint32_t v = 0; v < NW; ++v)
         {
-            r[0] += s_red[5 * v + 0], r[1] += s_red[5 * v + 1], r[2] += s_red[5 * v + 2];
-            r[3] = s_red[5 * v + 3] < r[3] ? s_red[5 * v + 3] : r[3];
-            r[4] = s_red[5 * v + 4] > r[4] ? s_red[5 * v + 4] : r[4];
+            r[0] += s_red[NR * v + 0], r[1] += s_red[NR * v + 1], r[2] += s_red[NR * v + 2];
+            r[3] = s_red[NR * v + 3] < r[3] ? s_red[NR * v + 3] : r[3];
+            r[4] = s_red[NR * v + 4] > r[4] ? s_red[NR * v + 4] : r[4];
+            if (KIND::VARH)
+                r[5] = s_red[NR * v + NR - 1u] > r[5] ? s_red[NR * v + NR - 1u] : r[5];
         }
+        if (KIND::VARH && r[5])
+            atomicMax(A.res + 7, (unsigned long long)r[5]);
         if (r[0])
             atomicAdd(A.res + 1, (unsigned long long)r[0]);
         if (r[1])
@@ -5426,39 +5471,41 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_count_kernel(pb_fgargs A)
 }
 
 // Offsets and map: one lane per source frame.  F(j), the output records before frame j, from the
-// scanned workgroup sums and a workgroup scan of K; the frame's first record starts at
-// off(j) - off(first) + 34 (F(j) - j) and every further one 34 + C after the last.
-__global__ __launch_bounds__(PB_FG_WT) void pb_frag_map_kernel(pb_fgargs A)
+// scanned row sums and a workgroup scan of K; X(j), the inserted bytes before it, likewise (VARH)
+// or 34 (F(j) - j).  The frame's first record starts at off(j) - off(first) + X(j) and every
+// further one a header and A.cut bytes after the last.
+template <class KIND>
+__device__ __forceinline__ void pb_cut_map(const pb_cutargs &A)
 {
-    __shared__ uint32_t s_w[PB_FG_WT / 64u];
+    constexpr uint32_t NW = PB_FG_WT / 64u, NS = KIND::VARH ? 2u : 1u;
+    __shared__ uint32_t s_w[NS][NW];
     const uint32_t tid = threadIdx.x;
     const uint64_t j = (uint64_t)blockIdx.x * PB_FG_WT + tid;
-    const uint32_t K = j < A.n ? A.kcnt[j] : 0u;
-    const uint32_t inc = pb_wave_scan(K);
+    const uint32_t kc = j < A.n ? A.kcnt[j] : 0u;
+    const uint32_t K = KIND::VARH ? kc & 0xFFFFu : kc, hq = KIND::VARH ? kc >> 16 : 0u, hl = 34u + 4u * hq;
+    const uint32_t ins = K ? (K - 1u) * hl : 0u;
+    const uint32_t inck = pb_wave_scan(K), incx = KIND::VARH ? pb_wave_scan(ins) : 0u;
     if ((tid & 63u) == 63u)
-        s_w[tid >> 6] = inc;
+    {
+        s_w[0][tid >> 6] = inck;
+        if (KIND::VARH)
+            s_w[NS - 1u][tid >> 6] = incx;
+    }
     __syncthreads();
-    uint32_t pre = inc - K;
+    uint32_t pre = inck - K, prex = incx - ins;
     for (uint32_t v = 0; v < (tid >> 6); ++v)
-        pre += s_w[v];
+    {
+        pre += s_w[0][v];
+        if (KIND::VARH)
+            prex += s_w[NS - 1u][v];
+    }
     if (j >= A.n)
         return;
     const uint64_t F = A.bsum[blockIdx.x] + pre;
     uint64_t o, ob;
     uint32_t L;
-    if (A.offsets)
-    {
-        ob = A.offsets[A.first];
-        o = A.offsets[A.first + j];
-        L = (uint32_t)(A.offsets[A.first + j + 1] - o);
-    }
-    else
-    {
-        ob = A.first * A.fixed_len;
-        o = (A.first + j) * A.fixed_len;
-        L = A.fixed_len;
-    }
-    const uint64_t O = (o - ob) + 34u * (F - j);
+    pb_rp_frame(A.offsets, A.first, A.fixed_len, A.offsets != nullptr, j, o, L, &ob);
+    const uint64_t O = (o - ob) + (KIND::VARH ? A.xsum[blockIdx.x] + prex : 34u * (F - j));
     if (K == 1u)
     {
         A.dst_offsets[F] = O;
@@ -5466,36 +5513,37 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_map_kernel(pb_fgargs A)
     }
     else
     {
-        const uint32_t step = 34u + A.C;
+        const uint32_t step = hl + A.cut;
         for (uint32_t i = 0; i < K; ++i)
         {
             A.dst_offsets[F + i] = O + (uint64_t)i * step;
-            A.map[F + i] = o | ((uint64_t)(i | PB_FG_M_SPLIT | (i + 1u == K ? PB_FG_M_LAST : 0u)) << PB_FG_M_ISH);
+            A.map[F + i] = o | ((uint64_t)KIND::bits(i, hq, i + 1u == K) << KIND::ISH);
         }
     }
     if (j + 1u == A.n)
-        A.dst_offsets[F + K] = O + L + 34u * (K - 1u);
+        A.dst_offsets[F + K] = O + L + ins;
 }
 
 // Writer, destination-owned as pb_encap_kernel: a workgroup owns `per` consecutive 4-KiB pages of
 // the output, a lane one aligned 16-B chunk of a page per step.  A window of record positions, source
-// positions and map bits is kept in LDS from page to page.  Per page one lane per fragment touching
-// it stages that fragment's 34-B header: the source frame's, with tot_len, the fragment field and
-// the checksum replaced, moved to the alignment it has in the output.  Every byte of a chunk that is
-// not in a staged header comes from the source at one shift: the one of the data of the record
+// positions and map bits is kept in LDS from page to page.  Per page one lane per piece touching
+// it stages that piece's header in its slot of s_hdr (KIND::hdw dwords each): the source frame's,
+// patched by KIND::header, moved to the alignment it has in the output.  Every byte of a chunk that
+// is not in a staged header comes from the source at one shift: the one of the data of the record
 // holding the chunk's first byte (between two insertions the shift is constant, an inserted header
-// is longer than a chunk, and a record shorter than a chunk is never a fragment).  At most three
+// is longer than a chunk, and a record shorter than a chunk is never a piece).  At most three
 // records' headers can reach into a chunk; a wave none of whose chunks meets a staged header or the
 // output's end takes the plain shifted copy, chosen per wave.
-__global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
+template <class KIND>
+__device__ __forceinline__ void pb_cut_write(const pb_cutargs &A, uint32_t *s_hdr)
 {
     __shared__ uint32_t s_rel[PB_FG_WIN];  // output start of record f0 + k relative to record f0's; 0xFFFFFFFF past the end
     __shared__ uint32_t s_h[PB_FG_WIN];    // its source frame's offset in src relative to record f0's
-    __shared__ uint32_t s_meta[PB_FG_WIN]; // map entry >> 48; 0 past the last record
-    __shared__ uint32_t s_hdr[PB_FG_HREC * PB_FG_HDW];
+    __shared__ uint32_t s_meta[PB_FG_WIN]; // map entry >> KIND::ISH; 0 past the last record
     const uint32_t tid = threadIdx.x;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-    const uint64_t hmask = (1ull << PB_FG_M_ISH) - 1u;
+    const uint64_t hmask = (1ull << KIND::ISH) - 1u;
+    const uint32_t hdw = KIND::hdw(A);
     uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
     if (p >= A.end16)
         return;
@@ -5539,7 +5587,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
                 {
                     const uint64_t m = A.map[ff];
                     hh = (uint32_t)((m & hmask) - hbase);
-                    mm = (uint32_t)(m >> PB_FG_M_ISH);
+                    mm = (uint32_t)(m >> KIND::ISH);
                 }
                 s_rel[k] = rel, s_h[k] = hh, s_meta[k] = mm;
             }
@@ -5552,39 +5600,19 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
         const uint32_t khi = kw + PB_FG_HREC - 1u < PB_FG_WIN - 1u ? kw + PB_FG_HREC - 1u : PB_FG_WIN - 1u;
         const uint32_t kend = pb_rp_find(s_rel, (uint32_t)d0 + 4095u, kw, khi);
 
-        // ---- header stage: the i-th record touching the page, if it is a fragment ----
+        // ---- header stage: the i-th record touching the page, if it is a piece ----
         for (uint32_t i = tid; kw + i <= kend; i += PB_FG_WT)
         {
             const uint32_t k = kw + i;
             if (k + 1u >= PB_FG_WIN)
                 continue;
             const uint32_t rs = s_rel[k], re = s_rel[k + 1u], meta = s_meta[k];
-            if (!(meta & PB_FG_M_SPLIT) || (int64_t)rs >= (int64_t)d0 + 4096)
+            if (!(meta & KIND::PIECE) || (int64_t)rs >= (int64_t)d0 + 4096)
                 continue;
-            // the source frame's first 34 bytes (the frame is longer than 82 B)
-            const uint64_t hsrc = hbase + s_h[k], i0 = hsrc >> 2;
-            const uint32_t sh = (uint32_t)hsrc & 3u;
-            uint32_t dd[10], T[PB_FG_HDW];
-#pragma unroll
-            for (uint32_t u = 0; u < 10u; ++u)
-                dd[u] = w[i0 + u];
-#pragma unroll
-            for (uint32_t u = 0; u < 9u; ++u)
-                T[u] = __builtin_amdgcn_alignbyte(dd[u + 1u], dd[u], sh);
-            T[9] = 0u;
-            const uint32_t fo = pb_bswap16(T[5] & 0xFFFFu);
-            const uint32_t tot = re - rs - 14u;
-            const uint32_t mf = (meta & PB_FG_M_LAST) ? (fo & 0x2000u) : 0x2000u;
-            const uint32_t frag = (fo & 0xC000u) | mf | (((fo & 0x1FFFu) + (meta & 0x7FFu) * (A.C >> 3)) & 0x1FFFu);
-            // the unchanged header words + tot_len + the fragment field, as little-endian halves: the
-            // one's complement sum commutes with the byte swap
-            const uint32_t s = (T[3] >> 16) + (T[4] >> 16) + (T[5] >> 16) + (T[6] >> 16) + pb_halves(T[7]) +
-                               (T[8] & 0xFFFFu) + pb_bswap16(tot) + pb_bswap16(frag);
-            T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
-            T[5] = (T[5] & 0xFFFF0000u) | pb_bswap16(frag);
-            T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
+            uint32_t T[KIND::TDW];
+            const uint32_t ndw = KIND::header(A, w, hbase + s_h[k], re - rs, meta, f0 + k, T);
             const int32_t hs = (int32_t)rs - d0; // the header's first byte in the page (below 0: before it)
-            pb_rp_stage(s_hdr + i * PB_FG_HDW, T, PB_FG_HDW, (uint32_t)hs & 3u);
+            pb_rp_stage(s_hdr + i * hdw, T, ndw, (uint32_t)hs & 3u);
         }
         __syncthreads();
 
@@ -5597,39 +5625,40 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
             const uint32_t k = pb_rp_find(s_rel, (uint32_t)d, kw, kend);
             const uint32_t rs = s_rel[k], meta = s_meta[k];
             const int32_t r = d - (int32_t)rs;
-            const bool frag = (meta & PB_FG_M_SPLIT) != 0u;
+            const bool piece = (meta & KIND::PIECE) != 0u;
+            const int32_t hl = (int32_t)KIND::hlen(meta);
             // the chunk's first byte in src, as data of its record
-            const int64_t a = (int64_t)(hbase + s_h[k]) + (frag ? (meta & 0x7FFu) * A.C : 0u) + r;
+            const int64_t a = (int64_t)(hbase + s_h[k]) + (piece ? (meta & KIND::IMASK) * A.cut : 0u) + r;
             const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
-            bool slow = (frag && r < 34) || hi < 16;
+            bool slow = (piece && r < hl) || hi < 16;
 #pragma unroll
             for (uint32_t c = 1; c < 3u; ++c)
-                slow = slow || (k + c < PB_FG_WIN && (s_meta[k + c] & PB_FG_M_SPLIT) && s_rel[k + c] < (uint32_t)(d + 16));
+                slow = slow || (k + c < PB_FG_WIN && (s_meta[k + c] & KIND::PIECE) && s_rel[k + c] < (uint32_t)(d + 16));
             pb_u32x4 v;
             if (__ballot(slow) == 0ull)
                 v = pb_rp_copy16(w, (uint64_t)a);
             else
             {
                 uint32_t o4[4] = {0u, 0u, 0u, 0u};
-                const int32_t lo = (frag && r < 34) ? 34 - r : 0; // the record's data starts here
+                const int32_t lo = (piece && r < hl) ? hl - r : 0; // the record's data starts here
                 if (lo < hi)
                     pb_rp_gather(w, a, lo, hi, o4);
 #pragma unroll
                 for (uint32_t c = 0; c < 3u; ++c)
                 {
                     const uint32_t kk = k + c;
-                    if (kk < PB_FG_WIN && (s_meta[kk] & PB_FG_M_SPLIT))
+                    if (kk < PB_FG_WIN && (s_meta[kk] & KIND::PIECE))
                     {
-                        const int32_t sa = (int32_t)s_rel[kk] - d, sb = sa + 34; // the header, in the chunk's bytes
+                        const int32_t sa = (int32_t)s_rel[kk] - d, sb = sa + (int32_t)KIND::hlen(s_meta[kk]); // the header, in the chunk's bytes
                         if (sa < 16 && sb > 0)
                         {
-                            const uint32_t *slot = s_hdr + (kk - kw) * PB_FG_HDW;
+                            const uint32_t *slot = s_hdr + (kk - kw) * hdw;
                             const int32_t hsp = (int32_t)s_rel[kk] - d0;
                             const int32_t ub = (16 * (int32_t)tid - (hsp & ~3)) >> 2;
 #pragma unroll
                             for (int t = 0; t < 4; ++t)
                             {
-                                const uint32_t val = (uint32_t)(ub + t) < PB_FG_HDW ? slot[(uint32_t)(ub + t)] : 0u;
+                                const uint32_t val = (uint32_t)(ub + t) < hdw ? slot[(uint32_t)(ub + t)] : 0u;
                                 const uint32_t m = pb_rp_lt(4 * t, sb) & ~pb_rp_lt(4 * t, sa);
                                 o4[t] = (o4[t] & ~m) | (val & m);
                             }
@@ -5649,252 +5678,272 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_fgargs A)
     }
 }
 
-// A fixed-length source none of whose frames can split: the range's bytes copied to byte 0 of dst,
-// zeros up to the next multiple of 16.  Pages and chunks as the writer's.
-__global__ __launch_bounds__(PB_FG_WT) void pb_frag_copy_kernel(pb_fgargs A)
+// A fixed-length source none of whose frames can split, for either call: the range's bytes (from
+// byte a0 of src) copied to byte 0 of dst, zeros up to the next multiple of 16.  Pages and chunks
+// as the writer's.
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_copy_kernel(const uint8_t *src, uint8_t *dst, uint64_t a0,
+                                                                uint64_t total, uint64_t end16, uint32_t per)
 {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-    const uint64_t a0 = A.first * A.fixed_len;
-    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12;
-    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(src);
+    uint64_t p = ((uint64_t)blockIdx.x * per) << 12;
+    for (uint32_t it = 0; it < per && p < end16; ++it, p += 4096u)
     {
         const uint64_t pc = p + 16u * threadIdx.x;
-        if (pc >= A.end16)
+        if (pc >= end16)
             continue;
-        const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
+        const int32_t hi = total - pc < 16u ? (int32_t)(total - pc) : 16;
         uint32_t o4[4];
         pb_rp_gather(w, (int64_t)(a0 + pc), 0, hi, o4);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
             o4[t] &= pb_rp_lt(4 * t, hi);
-        *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
+        *reinterpret_cast<pb_u32x4 *>(dst + pc) = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
     }
 }
 
-// stage 0: the result words, the count and the scan of its workgroup sums (the total lands in
-// res[0]); stage 1: dst->offsets, the map and the writer; stage 2: the plain copy
-extern "C" hipError_t pbk_launch_frag(const pb_fgargs *A, int stage, uint32_t grid, hipStream_t st)
+extern "C" hipError_t pbk_launch_cut_copy(const uint8_t *src, uint8_t *dst, uint64_t a0, uint64_t total,
+                                          uint64_t end16, uint32_t per, uint32_t grid, hipStream_t st)
+{
+    hipLaunchKernelGGL(pb_frag_copy_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, src, dst, a0, total, end16, per);
+    return hipGetLastError();
+}
+
+// ---------------- IPv4 fragmentation (pbgpu_fragment, DESIGN.md 5.11) ----------------
+// A.cut = C: the data bytes of a full fragment.  The inserted header is the frame's first 34 bytes
+// with tot_len, the fragment field and the checksum replaced.
+
+struct pb_fg_kind
+{
+    static constexpr bool VARH = false;
+    static constexpr uint32_t ISH = PB_FG_M_ISH, PIECE = PB_FG_M_SPLIT, IMASK = 0x7FFu, TDW = PB_FG_HDW;
+    static __device__ __forceinline__ uint32_t bits(uint32_t i, uint32_t, bool last)
+    {
+        return i | PB_FG_M_SPLIT | (last ? PB_FG_M_LAST : 0u);
+    }
+    static __device__ __forceinline__ uint32_t hlen(uint32_t) { return 34u; }
+    static __device__ __forceinline__ uint32_t hdw(const pb_cutargs &) { return PB_FG_HDW; }
+
+    // A frame that fits (L - 14 <= mtu) is never read; of the others bytes 12..23 come from aligned
+    // dwords inside the frame (it is longer than 82 B).  c[]: split, DF set, not plain IPv4
+    static __device__ __forceinline__ pb_cut_frame classify(const pb_cutargs &A, const uint32_t *w, uint64_t o,
+                                                            uint32_t L, uint32_t (&c)[3])
+    {
+        pb_cut_frame f = {1u, 0u, 0u, L, L};
+        if (L > A.mtu + 14u)
+        {
+            uint32_t b12, b20;
+            pb_cut_read12(w, o, b12, b20);
+            const uint32_t fo = pb_bswap16(b20 & 0xFFFFu);
+            if ((b12 & 0x00FFFFFFu) != 0x00450008u)
+                c[2] += 1;
+            else if ((fo & 0x4000u) && !(A.flags & PB_FG_IGNORE_DF))
+                c[1] += 1;
+            else
+            {
+                const uint32_t D = L - 34u;
+                f.K = pb_divq(D + A.cut - 1u, A.cdiv);
+                c[0] += 1;
+                f.lmax = 34u + A.cut;
+                f.lmin = 34u + D - (f.K - 1u) * A.cut;
+            }
+        }
+        return f;
+    }
+
+    // the source frame's first 34 bytes (the frame is longer than 82 B), patched for the fragment
+    // of len bytes that meta describes
+    static __device__ __forceinline__ uint32_t header(const pb_cutargs &A, const uint32_t *w, uint64_t hsrc,
+                                                      uint32_t len, uint32_t meta, uint64_t, uint32_t (&T)[TDW])
+    {
+        const uint64_t i0 = hsrc >> 2;
+        const uint32_t sh = (uint32_t)hsrc & 3u;
+        uint32_t dd[10];
+#pragma unroll
+        for (uint32_t u = 0; u < 10u; ++u)
+            dd[u] = w[i0 + u];
+#pragma unroll
+        for (uint32_t u = 0; u < 9u; ++u)
+            T[u] = __builtin_amdgcn_alignbyte(dd[u + 1u], dd[u], sh);
+        T[9] = 0u;
+        const uint32_t fo = pb_bswap16(T[5] & 0xFFFFu);
+        const uint32_t tot = len - 14u;
+        const uint32_t mf = (meta & PB_FG_M_LAST) ? (fo & 0x2000u) : 0x2000u;
+        const uint32_t frag = (fo & 0xC000u) | mf | (((fo & 0x1FFFu) + (meta & 0x7FFu) * (A.cut >> 3)) & 0x1FFFu);
+        // the unchanged header words + tot_len + the fragment field, as little-endian halves: the
+        // one's complement sum commutes with the byte swap
+        const uint32_t s = (T[3] >> 16) + (T[4] >> 16) + (T[5] >> 16) + (T[6] >> 16) + pb_halves(T[7]) +
+                           (T[8] & 0xFFFFu) + pb_bswap16(tot) + pb_bswap16(frag);
+        T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
+        T[5] = (T[5] & 0xFFFF0000u) | pb_bswap16(frag);
+        T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
+        return PB_FG_HDW;
+    }
+};
+
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_count_kernel(pb_cutargs A)
+{
+    pb_cut_count<pb_fg_kind>(A);
+}
+
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_map_kernel(pb_cutargs A)
+{
+    pb_cut_map<pb_fg_kind>(A);
+}
+
+__global__ __launch_bounds__(PB_FG_WT) void pb_frag_kernel(pb_cutargs A)
+{
+    __shared__ uint32_t s_hdr[PB_FG_HREC * PB_FG_HDW];
+    pb_cut_write<pb_fg_kind>(A, s_hdr);
+}
+
+// stage 0: the result words, the count and the scan of its row sums (the total lands in res[0]);
+// stage 1: dst->offsets, the map and the writer
+extern "C" hipError_t pbk_launch_frag(const pb_cutargs *A, int stage, uint32_t grid, hipStream_t st)
 {
     const uint32_t nblk = (uint32_t)((A->n + PB_FG_WT - 1u) / PB_FG_WT);
     if (stage == 0)
     {
-        hipLaunchKernelGGL(pb_frag_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_cut_init_kernel, dim3(1), dim3(64), 0, st, A->res);
         hipLaunchKernelGGL(pb_frag_count_kernel, dim3((nblk + PB_FG_CB - 1u) / PB_FG_CB), dim3(PB_FG_WT), 0, st, *A);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->bsum, nblk, (uint64_t *)A->res, (uint64_t)0);
     }
-    else if (stage == 1)
+    else
     {
         hipLaunchKernelGGL(pb_frag_map_kernel, dim3(nblk), dim3(PB_FG_WT), 0, st, *A);
         hipLaunchKernelGGL(pb_frag_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, *A);
     }
-    else
-        hipLaunchKernelGGL(pb_frag_copy_kernel, dim3(grid), dim3(PB_FG_WT), 0, st, *A);
     return hipGetLastError();
 }
 
 // ---------------- L4 segmentation (pbgpu_segment) ----------------
-// The fragmenter's shape with two differences.  The inserted header is 34 + H bytes (H = 8 for UDP,
-// the TCP header's own length else), so the output positions need a scan of the inserted bytes
-// beside the one of K; and every segment's L4 checksum needs the sum of its own slice of the source
-// payload, which a pass of its own takes (pb_seg_sum_kernel) before the writer stages the headers.
-// As there, everything that is not an inserted or patched header sits at its source position plus
-// the inserted bytes before it: segment i's slice ends where segment i + 1's begins.
+// A.cut = mss.  The inserted header is 34 + H bytes (H = 8 for UDP, the TCP header's own length
+// else), so the output positions need a scan of the inserted bytes beside the one of K; and every
+// segment's L4 checksum needs the sum of its own slice of the source payload, which a pass of its
+// own takes (pb_seg_sum_kernel) before the writer stages the headers: segment i's slice ends where
+// segment i + 1's begins.  A header slot is A.hdw dwords, sized by the longest header the count
+// pass met (dynamic LDS: 12 dwords for UDP, 15 for TCP without options, so that the slots do not
+// halve the workgroups per CU).
 
-__global__ __launch_bounds__(64) void pb_seg_init_kernel(unsigned long long *res)
+struct pb_sg_kind
 {
-    if (threadIdx.x < PB_SG_RES_DW)
-        res[threadIdx.x] = threadIdx.x == 4u ? 0xFFFFFFFFull : 0ull;
-}
-
-// Count: pb_frag_count_kernel's rows and reductions.  A frame with L - 42 <= mss is never read; of
-// the others (longer than 50 B) bytes 12..23 come from aligned dwords inside the frame, and byte
-// 46 of a TCP one of at least 54 B.  Per frame K and H / 4, per row the sums of K and of the
-// inserted bytes (K - 1)(34 + H); the largest H / 4 of a split frame sizes the writer's header slots.
-__global__ __launch_bounds__(PB_FG_WT) void pb_seg_count_kernel(pb_sgargs A)
-{
-    __shared__ uint32_t s_k[2][2][PB_FG_WT / 64u];
-    __shared__ uint32_t s_red[6 * (PB_FG_WT / 64u)];
-    const uint32_t tid = threadIdx.x, wv = tid >> 6;
-    const uint64_t nrow = (A.n + PB_FG_WT - 1u) / PB_FG_WT;
-    uint32_t tcp = 0, udp = 0, other = 0, omin = 0xFFFFFFFFu, omax = 0, hmax = 0;
-    for (uint32_t ri = 0; ri < PB_FG_CB; ++ri)
+    static constexpr bool VARH = true;
+    static constexpr uint32_t ISH = PB_SG_M_ISH, PIECE = PB_SG_M_SEG, IMASK = 0x1FFFu, TDW = PB_SG_HDW;
+    static __device__ __forceinline__ uint32_t bits(uint32_t i, uint32_t hq, bool last)
     {
-        const uint64_t row = (uint64_t)blockIdx.x * PB_FG_CB + ri;
-        if (row >= nrow)
-            break;
-        const uint64_t j = row * PB_FG_WT + tid;
-        uint32_t K = 0, X = 0;
-        if (j < A.n)
+        return i | hq << PB_SG_M_HSH | PB_SG_M_SEG | (last ? PB_SG_M_LAST : 0u);
+    }
+    static __device__ __forceinline__ uint32_t hlen(uint32_t meta) { return 34u + 4u * ((meta >> PB_SG_M_HSH) & 15u); }
+    static __device__ __forceinline__ uint32_t hdw(const pb_cutargs &A) { return A.hdw; }
+
+    // A frame with L - 42 <= mss is never read; of the others (longer than 50 B) bytes 12..23 come
+    // from aligned dwords inside the frame, and byte 46 of a TCP one of at least 54 B.  The largest
+    // H / 4 of a split frame sizes the writer's header slots.  c[]: split TCP, split UDP, neither
+    static __device__ __forceinline__ pb_cut_frame classify(const pb_cutargs &A, const uint32_t *w, uint64_t o,
+                                                            uint32_t L, uint32_t (&c)[3])
+    {
+        pb_cut_frame f = {1u, 0u, 0u, L, L};
+        if (L > A.cut + 42u)
         {
-            uint64_t o;
-            uint32_t L;
-            if (A.offsets)
+            uint32_t b12, b20;
+            pb_cut_read12(w, o, b12, b20);
+            const bool ip4 = (b12 & 0x00FFFFFFu) == 0x00450008u && !(pb_bswap16(b20 & 0xFFFFu) & 0x3FFFu);
+            const uint32_t proto = b20 >> 24;
+            uint32_t H = 0;
+            if (ip4 && proto == 17u)
+                H = 8u;
+            else if (ip4 && proto == 6u && L >= 54u)
             {
-                o = A.offsets[A.first + j];
-                L = (uint32_t)(A.offsets[A.first + j + 1] - o);
+                const uint64_t a46 = o + 46u;
+                const uint32_t h = ((w[a46 >> 2] >> (8u * ((uint32_t)a46 & 3u))) >> 4 & 0xFu) * 4u;
+                if (h >= 20u && 34u + h <= L)
+                    H = h;
             }
+            if (H == 0u)
+                c[2] += 1;
+            else if (L - 34u - H > A.cut)
+            {
+                const uint32_t P = L - 34u - H;
+                f.K = pb_divq(P + A.cut - 1u, A.cdiv);
+                f.hq = H >> 2;
+                f.X = (f.K - 1u) * (34u + H);
+                if (proto == 6u)
+                    c[0] += 1;
+                else
+                    c[1] += 1;
+                f.lmax = 34u + H + A.cut;
+                f.lmin = 34u + H + P - (f.K - 1u) * A.cut;
+            }
+        }
+        return f;
+    }
+
+    // The source frame's first 34 + H bytes (the frame is at least 9 B longer), patched for the
+    // segment of len bytes that meta describes, output record f: tot_len, the ID and the IPv4
+    // checksum, then the TCP sequence number and flags or the UDP length, and the L4 checksum closed
+    // from the pseudo header, the patched header words and the slice's sum.  All sums are in the
+    // frame domain (pb_vst_kernel).
+    static __device__ __forceinline__ uint32_t header(const pb_cutargs &A, const uint32_t *w, uint64_t hsrc,
+                                                      uint32_t len, uint32_t meta, uint64_t f, uint32_t (&T)[TDW])
+    {
+        const uint32_t hq = (meta >> PB_SG_M_HSH) & 15u, hl = 34u + 4u * hq, ndw = 9u + hq, si = meta & 0x1FFFu;
+        const uint64_t i0 = hsrc >> 2;
+        const uint32_t sh = (uint32_t)hsrc & 3u;
+        uint32_t dd[PB_SG_HDW];
+#pragma unroll
+        for (uint32_t u = 0; u < PB_SG_HDW; ++u)
+            dd[u] = u <= ndw ? w[i0 + u] : 0u;
+#pragma unroll
+        for (uint32_t u = 0; u + 1u < PB_SG_HDW; ++u)
+            T[u] = u < ndw ? __builtin_amdgcn_alignbyte(dd[u + 1u], dd[u], sh) : 0u;
+        T[PB_SG_HDW - 1u] = 0u;
+        const uint32_t tot = len - 14u, pi = len - hl;
+        uint32_t id = pb_bswap16(T[4] >> 16);
+        if (!(A.flags & PB_SG_FIXED_ID))
+            id = (id + si) & 0xFFFFu;
+        T[4] = pb_bswap16(tot) | pb_bswap16(id) << 16;
+        const uint32_t addr = (T[6] >> 16) + pb_halves(T[7]) + (T[8] & 0xFFFFu);
+        const uint32_t s = (T[3] >> 16) + pb_halves(T[4]) + pb_halves(T[5]) + addr;
+        T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
+        const bool tcp = hq != 2u;
+        if (tcp)
+        {
+            uint32_t seq = pb_bswap16(T[9] >> 16) << 16 | pb_bswap16(T[10] & 0xFFFFu);
+            seq += si * A.cut;
+            T[9] = (T[9] & 0xFFFFu) | pb_bswap16(seq >> 16) << 16;
+            T[10] = (T[10] & 0xFFFF0000u) | pb_bswap16(seq & 0xFFFFu);
+            const uint32_t clr = ((meta & PB_SG_M_LAST) ? 0u : 0x09u) | (si ? 0x80u : 0u);
+            T[11] &= ~(clr << 24);
+        }
+        else
+            T[9] = (T[9] & 0xFFFFu) | pb_bswap16(8u + pi) << 16;
+        if (!(A.flags & PB_SG_NO_L4))
+        {
+            if (tcp)
+                T[12] &= 0x0000FFFFu;
             else
-            {
-                o = (A.first + j) * A.fixed_len;
-                L = A.fixed_len;
-            }
-            K = 1;
-            uint32_t lmin = L, lmax = L, hq = 0;
-            if (L > A.mss + 42u)
-            {
-                const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-                const uint64_t a = o + 12u, i = a >> 2;
-                const uint32_t sh = (uint32_t)a & 3u;
-                const uint32_t d0 = w[i], d1 = w[i + 1], d2 = w[i + 2], d3 = w[i + 3];
-                const uint32_t b12 = __builtin_amdgcn_alignbyte(d1, d0, sh); // bytes 12..15
-                const uint32_t b20 = __builtin_amdgcn_alignbyte(d3, d2, sh); // bytes 20..23
-                const bool ip4 = (b12 & 0x00FFFFFFu) == 0x00450008u && !(pb_bswap16(b20 & 0xFFFFu) & 0x3FFFu);
-                const uint32_t proto = b20 >> 24;
-                uint32_t H = 0;
-                if (ip4 && proto == 17u)
-                    H = 8u;
-                else if (ip4 && proto == 6u && L >= 54u)
-                {
-                    const uint64_t a46 = o + 46u;
-                    const uint32_t h = ((w[a46 >> 2] >> (8u * ((uint32_t)a46 & 3u))) >> 4 & 0xFu) * 4u;
-                    if (h >= 20u && 34u + h <= L)
-                        H = h;
-                }
-                if (H == 0u)
-                    other += 1;
-                else if (L - 34u - H > A.mss)
-                {
-                    const uint32_t P = L - 34u - H;
-                    K = pb_divq(P + A.mss - 1u, A.mdiv);
-                    hq = H >> 2;
-                    X = (K - 1u) * (34u + H);
-                    if (proto == 6u)
-                        tcp += 1;
-                    else
-                        udp += 1;
-                    lmax = 34u + H + A.mss;
-                    lmin = 34u + H + P - (K - 1u) * A.mss;
-                }
-            }
-            omin = lmin < omin ? lmin : omin;
-            omax = lmax > omax ? lmax : omax;
-            hmax = hq > hmax ? hq : hmax;
-            A.kcnt[j] = K | hq << 16;
-        }
-        uint32_t sumK = K, sumX = X;
+                T[10] &= 0xFFFF0000u;
+            uint32_t l4 = addr + ((tcp ? 6u : 17u) << 8) + pb_bswap16(4u * hq + pi) + (T[8] >> 16) + A.psum[f];
 #pragma unroll
-        for (uint32_t dd = 32; dd > 0; dd >>= 1)
-        {
-            sumK += __shfl_xor(sumK, dd, 64);
-            sumX += __shfl_xor(sumX, dd, 64);
+            for (uint32_t u = 9; u + 1u < PB_SG_HDW; ++u)
+                l4 += u < 8u + hq ? pb_halves(T[u]) : (u == 8u + hq ? T[u] & 0xFFFFu : 0u);
+            uint32_t c = ~pb_fold(l4) & 0xFFFFu;
+            if (tcp)
+                T[12] |= c << 16;
+            else
+                T[10] |= c ? c : 0xFFFFu;
         }
-        if ((tid & 63u) == 0)
-            s_k[ri & 1u][0][wv] = sumK, s_k[ri & 1u][1][wv] = sumX; // two sets, as pb_frag_count_kernel
-        __syncthreads();
-        if (tid == 0)
-        {
-            uint32_t t = 0, x = 0;
-#pragma unroll
-            for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
-                t += s_k[ri & 1u][0][v], x += s_k[ri & 1u][1][v];
-            A.bsum[row] = t;
-            A.xsum[row] = x;
-        }
+        return ndw + 1u;
     }
-#pragma unroll
-    for (uint32_t dd = 32; dd > 0; dd >>= 1)
-    {
-        tcp += __shfl_xor(tcp, dd, 64);
-        udp += __shfl_xor(udp, dd, 64);
-        other += __shfl_xor(other, dd, 64);
-        const uint32_t mn = __shfl_xor(omin, dd, 64), mx = __shfl_xor(omax, dd, 64), hx = __shfl_xor(hmax, dd, 64);
-        omin = mn < omin ? mn : omin;
-        omax = mx > omax ? mx : omax;
-        hmax = hx > hmax ? hx : hmax;
-    }
-    if ((tid & 63u) == 0)
-    {
-        s_red[6 * wv + 0] = tcp, s_red[6 * wv + 1] = udp, s_red[6 * wv + 2] = other;
-        s_red[6 * wv + 3] = omin, s_red[6 * wv + 4] = omax, s_red[6 * wv + 5] = hmax;
-    }
-    __syncthreads();
-    if (tid == 0)
-    {
-        uint32_t r[6] = {0, 0, 0, 0xFFFFFFFFu, 0, 0};
-#pragma unroll
-        for (uint32_t v = 0; v < PB_FG_WT / 64u; ++v)
-        {
-            r[0] += s_red[6 * v + 0], r[1] += s_red[6 * v + 1], r[2] += s_red[6 * v + 2];
-            r[3] = s_red[6 * v + 3] < r[3] ? s_red[6 * v + 3] : r[3];
-            r[4] = s_red[6 * v + 4] > r[4] ? s_red[6 * v + 4] : r[4];
-            r[5] = s_red[6 * v + 5] > r[5] ? s_red[6 * v + 5] : r[5];
-        }
-        if (r[5])
-            atomicMax(A.res + 7, (unsigned long long)r[5]);
-        if (r[0])
-            atomicAdd(A.res + 1, (unsigned long long)r[0]);
-        if (r[1])
-            atomicAdd(A.res + 2, (unsigned long long)r[1]);
-        if (r[2])
-            atomicAdd(A.res + 3, (unsigned long long)r[2]);
-        atomicMin(A.res + 4, (unsigned long long)r[3]);
-        atomicMax(A.res + 5, (unsigned long long)r[4]);
-    }
+};
+
+__global__ __launch_bounds__(PB_FG_WT) void pb_seg_count_kernel(pb_cutargs A)
+{
+    pb_cut_count<pb_sg_kind>(A);
 }
 
-// Offsets and map: one lane per source frame.  F(j), the output records before frame j, and X(j),
-// the inserted bytes before it, from the two scanned row sums and two workgroup scans; the frame's
-// first record starts at off(j) - off(first) + X(j) and every further one 34 + H + mss after the last.
-__global__ __launch_bounds__(PB_FG_WT) void pb_seg_map_kernel(pb_sgargs A)
+__global__ __launch_bounds__(PB_FG_WT) void pb_seg_map_kernel(pb_cutargs A)
 {
-    __shared__ uint32_t s_w[2][PB_FG_WT / 64u];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t j = (uint64_t)blockIdx.x * PB_FG_WT + tid;
-    const uint32_t kc = j < A.n ? A.kcnt[j] : 0u;
-    const uint32_t K = kc & 0xFFFFu, hq = kc >> 16, hl = 34u + 4u * hq;
-    const uint32_t ins = K ? (K - 1u) * hl : 0u;
-    const uint32_t inck = pb_wave_scan(K), incx = pb_wave_scan(ins);
-    if ((tid & 63u) == 63u)
-        s_w[0][tid >> 6] = inck, s_w[1][tid >> 6] = incx;
-    __syncthreads();
-    uint32_t pre = inck - K, prex = incx - ins;
-    for (uint32_t v = 0; v < (tid >> 6); ++v)
-        pre += s_w[0][v], prex += s_w[1][v];
-    if (j >= A.n)
-        return;
-    const uint64_t F = A.bsum[blockIdx.x] + pre;
-    uint64_t o, ob;
-    uint32_t L;
-    if (A.offsets)
-    {
-        ob = A.offsets[A.first];
-        o = A.offsets[A.first + j];
-        L = (uint32_t)(A.offsets[A.first + j + 1] - o);
-    }
-    else
-    {
-        ob = A.first * A.fixed_len;
-        o = (A.first + j) * A.fixed_len;
-        L = A.fixed_len;
-    }
-    const uint64_t O = (o - ob) + A.xsum[blockIdx.x] + prex;
-    if (K == 1u)
-    {
-        A.dst_offsets[F] = O;
-        A.map[F] = o;
-    }
-    else
-    {
-        const uint32_t step = hl + A.mss;
-        for (uint32_t i = 0; i < K; ++i)
-        {
-            A.dst_offsets[F + i] = O + (uint64_t)i * step;
-            A.map[F + i] =
-                o | ((uint64_t)(i | hq << PB_SG_M_HSH | PB_SG_M_SEG | (i + 1u == K ? PB_SG_M_LAST : 0u)) << PB_SG_M_ISH);
-        }
-    }
-    if (j + 1u == A.n)
-        A.dst_offsets[F + K] = O + L + ins;
+    pb_cut_map<pb_sg_kind>(A);
 }
 
 // Sum: a group of G lanes per output record; a segment's group sums its slice of the source payload
@@ -5902,7 +5951,7 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_seg_map_kernel(pb_sgargs A)
 // edge chunks byte-masked, the folded sum byte-swapped where the slice starts on an odd address.
 // A lane adds at most 65,493 / 16 / 8 chunks of at most 8 * 0xFFFF each: no carry is lost.
 template <int G>
-__global__ __launch_bounds__(PB_FG_WT) void pb_seg_sum_kernel(pb_sgargs A)
+__global__ __launch_bounds__(PB_FG_WT) void pb_seg_sum_kernel(pb_cutargs A)
 {
     constexpr uint32_t NG = PB_FG_WT / G;
     const uint32_t tid = threadIdx.x, grp = tid / G, gl = tid % G;
@@ -5917,9 +5966,9 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_seg_sum_kernel(pb_sgargs A)
         seg = (meta & PB_SG_M_SEG) != 0u;
         if (seg)
         {
-            const uint32_t hl = 34u + 4u * ((meta >> PB_SG_M_HSH) & 15u);
+            const uint32_t hl = pb_sg_kind::hlen(meta);
             const uint32_t pi = (uint32_t)(A.dst_offsets[f + 1] - A.dst_offsets[f]) - hl; // at least 1
-            lo = (m & ((1ull << PB_SG_M_ISH) - 1u)) + hl + (uint64_t)(meta & 0x1FFFu) * A.mss;
+            lo = (m & ((1ull << PB_SG_M_ISH) - 1u)) + hl + (uint64_t)(meta & 0x1FFFu) * A.cut;
             const uint64_t hi = lo + pi;
             const uint64_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
             for (uint64_t ch = c0 + gl; ch <= c1; ch += G)
@@ -5948,210 +5997,21 @@ __global__ __launch_bounds__(PB_FG_WT) void pb_seg_sum_kernel(pb_sgargs A)
         A.psum[f] = s;
 }
 
-// Writer: pb_frag_kernel's pages, window and chunks; the staged header is the record's own 34 + H
-// bytes.  The header lane patches tot_len, the ID and the IPv4 checksum, then the TCP sequence
-// number and flags or the UDP length, and closes the L4 checksum from the pseudo header, the patched
-// header words and the slice's sum.  All sums are in the frame domain (pb_vst_kernel).  At most
-// three records' headers can reach into a chunk, as there: a segment is longer than 42 B.  A header
-// slot is A.hdw dwords, sized by the longest header the count pass met (dynamic LDS: 12 dwords for
-// UDP, 15 for TCP without options, so that the slots do not halve the workgroups per CU).
-__global__ __launch_bounds__(PB_FG_WT) void pb_seg_kernel(pb_sgargs A)
+__global__ __launch_bounds__(PB_FG_WT) void pb_seg_kernel(pb_cutargs A)
 {
     extern __shared__ uint32_t s_hdr[]; // PB_FG_HREC slots of A.hdw dwords
-    __shared__ uint32_t s_rel[PB_FG_WIN];  // output start of record f0 + k relative to record f0's; 0xFFFFFFFF past the end
-    __shared__ uint32_t s_h[PB_FG_WIN];    // its source frame's offset in src relative to record f0's
-    __shared__ uint32_t s_meta[PB_FG_WIN]; // map entry >> 44; 0 past the last record
-    const uint32_t tid = threadIdx.x;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-    const uint64_t hmask = (1ull << PB_SG_M_ISH) - 1u;
-    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
-    if (p >= A.end16)
-        return;
-    // f0: the record holding the first page's first byte (p is below the output's last byte)
-    uint64_t f0 = 0;
-    {
-        uint64_t lo = 0, hi = A.n_out - 1u;
-        while (lo < hi)
-        {
-            const uint64_t mid = lo + (hi - lo + 1) / 2;
-            if (A.dst_offsets[mid] <= p)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
-        f0 = lo;
-    }
-    int32_t d0 = (int32_t)(p - A.dst_offsets[f0]); // the page's first byte relative to record f0's start
-    uint64_t hbase = 0;
-    bool have_win = false;
-    uint32_t kw = 0; // the window's index of the record holding the page's first byte
-    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
-    {
-        if (!have_win || (int64_t)s_rel[PB_FG_WIN - 1u] <= (int64_t)d0 + 4095)
-        {
-            if (have_win) // the window moves to that record
-            {
-                f0 += kw;
-                d0 -= (int32_t)s_rel[kw];
-            }
-            __syncthreads(); // the window's readers are done
-            const uint64_t g = A.dst_offsets[f0];
-            hbase = A.map[f0] & hmask;
-            for (uint32_t k = tid; k < PB_FG_WIN; k += PB_FG_WT)
-            {
-                const uint64_t ff = f0 + k;
-                uint32_t rel = 0xFFFFFFFFu, hh = 0, mm = 0;
-                if (ff <= A.n_out)
-                    rel = (uint32_t)(A.dst_offsets[ff] - g);
-                if (ff < A.n_out)
-                {
-                    const uint64_t m = A.map[ff];
-                    hh = (uint32_t)((m & hmask) - hbase);
-                    mm = (uint32_t)(m >> PB_SG_M_ISH);
-                }
-                s_rel[k] = rel, s_h[k] = hh, s_meta[k] = mm;
-            }
-            have_win = true;
-            kw = 0;
-        }
-        __syncthreads(); // the window is in place, the last page's header readers are done
-        const uint32_t khi = kw + PB_FG_HREC - 1u < PB_FG_WIN - 1u ? kw + PB_FG_HREC - 1u : PB_FG_WIN - 1u;
-        const uint32_t kend = pb_rp_find(s_rel, (uint32_t)d0 + 4095u, kw, khi);
-
-        // ---- header stage: the i-th record touching the page, if it is a segment ----
-        for (uint32_t i = tid; kw + i <= kend; i += PB_FG_WT)
-        {
-            const uint32_t k = kw + i;
-            if (k + 1u >= PB_FG_WIN)
-                continue;
-            const uint32_t rs = s_rel[k], re = s_rel[k + 1u], meta = s_meta[k];
-            if (!(meta & PB_SG_M_SEG) || (int64_t)rs >= (int64_t)d0 + 4096)
-                continue;
-            const uint32_t hq = (meta >> PB_SG_M_HSH) & 15u, hl = 34u + 4u * hq, ndw = 9u + hq, si = meta & 0x1FFFu;
-            // the source frame's first 34 + H bytes (the frame is at least 9 B longer)
-            const uint64_t hsrc = hbase + s_h[k], i0 = hsrc >> 2;
-            const uint32_t sh = (uint32_t)hsrc & 3u;
-            uint32_t dd[PB_SG_HDW], T[PB_SG_HDW];
-#pragma unroll
-            for (uint32_t u = 0; u < PB_SG_HDW; ++u)
-                dd[u] = u <= ndw ? w[i0 + u] : 0u;
-#pragma unroll
-            for (uint32_t u = 0; u + 1u < PB_SG_HDW; ++u)
-                T[u] = u < ndw ? __builtin_amdgcn_alignbyte(dd[u + 1u], dd[u], sh) : 0u;
-            T[PB_SG_HDW - 1u] = 0u;
-            const uint32_t tot = re - rs - 14u, pi = re - rs - hl;
-            uint32_t id = pb_bswap16(T[4] >> 16);
-            if (!(A.flags & PB_SG_FIXED_ID))
-                id = (id + si) & 0xFFFFu;
-            T[4] = pb_bswap16(tot) | pb_bswap16(id) << 16;
-            const uint32_t addr = (T[6] >> 16) + pb_halves(T[7]) + (T[8] & 0xFFFFu);
-            const uint32_t s = (T[3] >> 16) + pb_halves(T[4]) + pb_halves(T[5]) + addr;
-            T[6] = (T[6] & 0xFFFF0000u) | (~pb_fold(s) & 0xFFFFu);
-            const bool tcp = hq != 2u;
-            if (tcp)
-            {
-                uint32_t seq = pb_bswap16(T[9] >> 16) << 16 | pb_bswap16(T[10] & 0xFFFFu);
-                seq += si * A.mss;
-                T[9] = (T[9] & 0xFFFFu) | pb_bswap16(seq >> 16) << 16;
-                T[10] = (T[10] & 0xFFFF0000u) | pb_bswap16(seq & 0xFFFFu);
-                const uint32_t clr = ((meta & PB_SG_M_LAST) ? 0u : 0x09u) | (si ? 0x80u : 0u);
-                T[11] &= ~(clr << 24);
-            }
-            else
-                T[9] = (T[9] & 0xFFFFu) | pb_bswap16(8u + pi) << 16;
-            if (!(A.flags & PB_SG_NO_L4))
-            {
-                if (tcp)
-                    T[12] &= 0x0000FFFFu;
-                else
-                    T[10] &= 0xFFFF0000u;
-                uint32_t l4 = addr + ((tcp ? 6u : 17u) << 8) + pb_bswap16(4u * hq + pi) + (T[8] >> 16) + A.psum[f0 + k];
-#pragma unroll
-                for (uint32_t u = 9; u + 1u < PB_SG_HDW; ++u)
-                    l4 += u < 8u + hq ? pb_halves(T[u]) : (u == 8u + hq ? T[u] & 0xFFFFu : 0u);
-                uint32_t c = ~pb_fold(l4) & 0xFFFFu;
-                if (tcp)
-                    T[12] |= c << 16;
-                else
-                    T[10] |= c ? c : 0xFFFFu;
-            }
-            const int32_t hs = (int32_t)rs - d0; // the header's first byte in the page (below 0: before it)
-            pb_rp_stage(s_hdr + i * A.hdw, T, ndw + 1u, (uint32_t)hs & 3u);
-        }
-        __syncthreads();
-
-        // ---- chunks ----
-        const int32_t d = d0 + 16 * (int32_t)tid;
-        const uint64_t pc = p + 16u * tid;
-        if (pc < A.end16)
-        {
-            // the chunk starts r bytes into record f0 + k (pc is below the output's last byte)
-            const uint32_t k = pb_rp_find(s_rel, (uint32_t)d, kw, kend);
-            const uint32_t rs = s_rel[k], meta = s_meta[k];
-            const int32_t r = d - (int32_t)rs;
-            const bool seg = (meta & PB_SG_M_SEG) != 0u;
-            const int32_t hl = 34 + 4 * (int32_t)((meta >> PB_SG_M_HSH) & 15u);
-            // the chunk's first byte in src, as data of its record
-            const int64_t a = (int64_t)(hbase + s_h[k]) + (seg ? (meta & 0x1FFFu) * A.mss : 0u) + r;
-            const int32_t hi = A.total - pc < 16u ? (int32_t)(A.total - pc) : 16;
-            bool slow = (seg && r < hl) || hi < 16;
-#pragma unroll
-            for (uint32_t c = 1; c < 3u; ++c)
-                slow = slow || (k + c < PB_FG_WIN && (s_meta[k + c] & PB_SG_M_SEG) && s_rel[k + c] < (uint32_t)(d + 16));
-            pb_u32x4 v;
-            if (__ballot(slow) == 0ull)
-                v = pb_rp_copy16(w, (uint64_t)a);
-            else
-            {
-                uint32_t o4[4] = {0u, 0u, 0u, 0u};
-                const int32_t lo = (seg && r < hl) ? hl - r : 0; // the record's data starts here
-                if (lo < hi)
-                    pb_rp_gather(w, a, lo, hi, o4);
-#pragma unroll
-                for (uint32_t c = 0; c < 3u; ++c)
-                {
-                    const uint32_t kk = k + c;
-                    if (kk < PB_FG_WIN && (s_meta[kk] & PB_SG_M_SEG))
-                    {
-                        const int32_t hk = 34 + 4 * (int32_t)((s_meta[kk] >> PB_SG_M_HSH) & 15u);
-                        const int32_t sa = (int32_t)s_rel[kk] - d, sb = sa + hk; // the header, in the chunk's bytes
-                        if (sa < 16 && sb > 0)
-                        {
-                            const uint32_t *slot = s_hdr + (kk - kw) * A.hdw;
-                            const int32_t hsp = (int32_t)s_rel[kk] - d0;
-                            const int32_t ub = (16 * (int32_t)tid - (hsp & ~3)) >> 2;
-#pragma unroll
-                            for (int t = 0; t < 4; ++t)
-                            {
-                                const uint32_t val = (uint32_t)(ub + t) < A.hdw ? slot[(uint32_t)(ub + t)] : 0u;
-                                const uint32_t m = pb_rp_lt(4 * t, sb) & ~pb_rp_lt(4 * t, sa);
-                                o4[t] = (o4[t] & ~m) | (val & m);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    o4[t] &= pb_rp_lt(4 * t, hi); // zeros past the output's last byte
-                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
-            }
-            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
-        }
-        // the next page's first byte is in the record holding this page's last byte, or the one after
-        d0 += 4096;
-        kw = s_rel[kend + 1u] <= (uint32_t)d0 ? kend + 1u : kend;
-    }
+    pb_cut_write<pb_sg_kind>(A, s_hdr);
 }
 
 // stage 0: the result words, the count and the two scans of its row sums (the totals land in res[0]
 // and res[6]); stage 1: dst->offsets and the map, the slice sums (G lanes per record, 0: none) and
-// the writer.  The plain copy of a source that cannot split is pbk_launch_frag's stage 2.
-extern "C" hipError_t pbk_launch_seg(const pb_sgargs *A, int stage, int G, uint32_t grid, hipStream_t st)
+// the writer
+extern "C" hipError_t pbk_launch_seg(const pb_cutargs *A, int stage, int G, uint32_t grid, hipStream_t st)
 {
     const uint32_t nblk = (uint32_t)((A->n + PB_FG_WT - 1u) / PB_FG_WT);
     if (stage == 0)
     {
-        hipLaunchKernelGGL(pb_seg_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_cut_init_kernel, dim3(1), dim3(64), 0, st, A->res);
         hipLaunchKernelGGL(pb_seg_count_kernel, dim3((nblk + PB_FG_CB - 1u) / PB_FG_CB), dim3(PB_FG_WT), 0, st, *A);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->bsum, nblk, (uint64_t *)A->res, (uint64_t)0);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->xsum, nblk, (uint64_t *)A->res, (uint64_t)6);
@@ -6284,16 +6144,7 @@ __global__ __launch_bounds__(PB_SP_WT) void pb_stamp_kernel(pb_spargs A)
             break;
         uint64_t o;
         uint32_t L;
-        if (VAR)
-        {
-            o = A.offsets[A.first + j];
-            L = (uint32_t)(A.offsets[A.first + j + 1] - o);
-        }
-        else
-        {
-            o = (A.first + j) * A.fixed_len;
-            L = A.fixed_len;
-        }
+        pb_rp_frame(A.offsets, A.first, A.fixed_len, VAR, j, o, L);
         if (L < 34u)
         {
             other += 1;

@@ -539,3 +539,62 @@ def test_output_past_4_gib(ctx):
             dst.free()
     finally:
         fb.free()
+
+
+# ------------------------------------------------------------------ 9. one scratch under both calls
+def _one_call(ctx, call, refs, cnt):
+    """One fragment or segment call into a watched destination: every byte, the result, the offsets."""
+    ref = b"".join(refs)
+    total, r16 = len(ref), (len(ref) + 15) & ~15
+    dst, cap = fresh_dst(ctx, total, len(refs))
+    try:
+        res = call(dst)
+        assert {k: int(getattr(res, k)) for k in cnt} == cnt
+        got = dst.stream(cap)
+        assert np.array_equal(got[:total], np.frombuffer(ref, dtype=np.uint8))
+        assert not got[total:r16].any() and (got[r16:] == 0xA5).all()
+        assert (int(dst.f.n_frames), int(dst.f.fixed_len), int(dst.f.total_bytes)) == (len(refs), 0, total)
+        want_off = np.concatenate([[0], np.cumsum([len(r) for r in refs])]).astype(np.uint64)
+        assert np.array_equal(dst.offsets(), want_off)
+    finally:
+        dst.free()
+
+
+def test_fragment_and_segment_share_their_scratch():
+    """pbgpu_fragment and pbgpu_segment keep one count scratch, one map and one slice-sum buffer in
+    the context, and lay the count scratch out differently (one row sum, or two).  On one fresh
+    context a small segment call, a fragment call whose count takes two workgroups (4,200 frames:
+    all three buffers grow), the first call again, then the two _size calls on the other kind's
+    buffer and a small fragment call: each output whole against pyseg / pyfrag."""
+    small = []
+    for j in range(40):
+        if j % 5 == 4:
+            small.append(sf.payload(14 + j, j))
+        elif j % 5 == 3:
+            small.append(sf.tcp(700 + 37 * j, j, ident=j, seq=j * 977, flags=j, H=(20, 24, 60)[j % 3]))
+        else:
+            small.append(frame_of(("udp", "tcp")[j & 1], 60 + 83 * j, 500 + j))
+    kinds = [frame_of(("udp", "tcp")[j & 1], 1621, 40 + j) for j in range(8)]
+    large = [kinds[(j * 5 + j // 8) % 8] for j in range(4200)]
+    assert len(large) > 16 * 256  # the count's rows per workgroup times its frames per row
+    seg_small = pyseg.segment_all(small, 536, 0)
+    frag_small = pyfrag.fragment_all(small, 576, True)
+    frag_large = pyfrag.fragment_all(large, 576, True)
+    seg_large, _ = pyseg.segment_all(large, 536, 0)
+    assert frag_large[1]["n_split"] == 4200 and seg_small[1]["n_out"] > 40 and frag_small[1]["n_out"] > 40
+    ctx = GpuContext(0)
+    try:
+        sd, so = pack(small)
+        fs, fl = uploaded(ctx, sd, off=so), uploaded(ctx, pack(large)[0], flen=1621)
+        try:
+            _one_call(ctx, lambda d: fs.segment(d, 0, 40, 536), *seg_small)
+            _one_call(ctx, lambda d: fl.fragment(d, 0, 4200, 576, True), *frag_large)
+            _one_call(ctx, lambda d: fs.segment(d, 0, 40, 536), *seg_small)
+            assert ctx.fragment_size(fs, 0, 40, 576, True) == (len(frag_small[0]), sum(map(len, frag_small[0])))
+            assert ctx.segment_size(fl, 0, 4200, 536) == (len(seg_large), sum(map(len, seg_large)))
+            _one_call(ctx, lambda d: fs.fragment(d, 0, 40, 576, True), *frag_small)
+        finally:
+            fs.free()
+            fl.free()
+    finally:
+        ctx.close()
