@@ -136,11 +136,24 @@ int pbgpu_build(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uint64_t 
  * first_iter[i] + n_iter[i]) of sequence seq_idx[i] into outs[i], exactly as
  * pbgpu_build() would (same frames, offsets and counters).  The reference runs
  * its sequences side by side (sequence.c:741-762, one thread group per
- * sequence); configs[4]'s three (64-B UDP, 60-B TCP SYN, 98-B ICMP echo, each
- * into its own 4-KiB-aligned buffer) are built by one fused launch
- * (pb_batch_kernel), any other set by one launch per part (also when a part's
- * sequence was loaded with PBGPU_BATCH=0).  Every part's arguments are checked
- * first: on an error no part is built and the counters are unchanged. */
+ * sequence).  One fused launch (pb_batch_kernel) builds a call of n == 3 distinct
+ * sequences, in any order, one of each kind, each with one payload and one frame length:
+ *   1  UDP, random payload, 64 B;
+ *   2  TCP, random payload, 56 or 60 B (64 B when loaded under PBGPU_XP_FORCE=1);
+ *   3  ICMP, static payload (exact, string or isstatic), 66, 70, ... 126 B (2 mod 4); its part
+ *      copies the stream's image (pb_ximg_body) unless the sequence was loaded under
+ *      PBGPU_XP_IMG=0, PBGPU_XP_FORCE=1 or PBGPU_KERNEL = gpf, stage, vstage or vpage (the page
+ *      body then; a value PBGPU_KERNEL does not know is the default).
+ * configs[4]'s three (64-B UDP, 60-B TCP SYN, 98-B ICMP echo) are one such set; header fields,
+ * checksum options and rules do not matter.  Environment, read when a sequence is loaded: no
+ * fused form under PBGPU_BATCH=0 or PBGPU_KERNEL=linear, for a 64-B UDP sequence under
+ * PBGPU_XP_FORCE=1, for kinds 2 and 3 under PBGPU_KERNEL=nopage and for kind 3 under
+ * PBGPU_XP_STATIC=0 (PBGPU_XP_FORCE=1 overrides the last two); read at pbgpu_open:
+ * PBGPU_BATCH_WGT=256 (the launch's block size, 512 otherwise).  The call must also give every
+ * part n_iter > 0 and a buffer of its own whose data is 4-KiB aligned.  Any other call is built by
+ * one launch per part that has frames, with identical frames, offsets and counters.  Every
+ * part's arguments are checked first: on an error no part is built and the counters are
+ * unchanged. */
 int pbgpu_build_batch(pbgpu_ctx *ctx, uint32_t n, const uint16_t *seq_idx, const uint64_t *first_iter,
                       const uint64_t *n_iter, pbgpu_frames *const *outs);
 

@@ -1112,8 +1112,9 @@ __global__ __launch_bounds__(WGT) __attribute__((amdgpu_num_sgpr(80))) void pb_x
 // g_j) (o_j a multiple of 8, so a part's workgroup b stays on XCD b % 8 and keeps its page
 // ownership) and runs its kernel's body on its own kargs; the dispatcher starts part j + 1's
 // workgroups while part j's last ones finish.  One block size (WGT) for all parts: the 64-B part
-// runs pb_xsmall_body with WGT / 64 pages per workgroup.  Kinds (pbk_batch_kind): 1 the 64-B
-// random-payload UDP page kernel, 2 the 60-B random-payload TCP one, 3 the 98-B static-payload ICMP.
+// runs pb_xsmall_wg_body with WGT / 64 pages per workgroup.  Kinds (pbk_batch_kind): 1 the 64-B
+// random-payload UDP page kernel, 2 the random-payload TCP one (56, 60, forced 64 B), 3 the
+// static-payload ICMP one at 2 mod 4 (66 ... 126 B; configs[4] has 60 and 98 B).
 struct pb_batch_args
 {
     pb_kargs K[3];
