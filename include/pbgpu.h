@@ -653,6 +653,13 @@ int pbgpu_page_grid(pbgpu_ctx *ctx, uint64_t npages, uint32_t *per, uint32_t *gr
 /* Name of the frame-build kernel variant a loaded sequence launches
  * (as rocprofv3 reports it). */
 int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n);
+/* Test hook: what pbgpu_load_sequence would choose for this sequence under the present PBGPU_*
+ * environment, with no context and no device.  One line: the kernel's name as pbgpu_kernel_name
+ * prints it, " | ", then key=value pairs (flags, fixed_len, min_flen, max_flen, fpi, batch, orbit,
+ * img_np, img_solo, then the shape fields the chosen kernel reads).  -EINVAL exactly where
+ * pbgpu_load_sequence refuses the sequence. */
+int pbgpu_plan_describe(uint16_t seq_idx, const pb_sequence_t *seq, const pb_rules_t *rules, uint64_t seed_base,
+                        char *buf, size_t n);
 
 /* ABI self-description for FFI bindings: sizes / offsets of the structs above.
  * which: 0 sizeof(pb_sequence_t), 1 sizeof(pb_payload_opt_t), 2 sizeof(pbgpu_frames),

@@ -26,9 +26,10 @@
 
 #include "../../include/pbgpu.h"
 #include "pb_device.h"
+#include "pb_plan.h"
 
-extern "C" hipError_t pbk_launch_build(const pb_kargs *K, hipStream_t st);
-extern "C" uint32_t pbk_build_grid(const pb_kargs *K);
+extern "C" hipError_t pbk_launch_build(const pb_kargs *K, pb_kern kern, hipStream_t st);
+extern "C" uint32_t pbk_build_grid(const pb_kargs *K, pb_kern kern);
 extern "C" int pbk_batch_kind(const pb_kargs *K);
 extern "C" hipError_t pbk_launch_batch(const pb_kargs *Ks, uint32_t wgt, hipStream_t st);
 extern "C" hipError_t pbk_launch_ctr_fold(const uint32_t *slots, uint64_t n, uint32_t pairs,
@@ -63,7 +64,6 @@ extern "C" hipError_t pbk_launch_scatter_fixed(const uint8_t *src, uint32_t flen
 
 #define PB_JUMP_N (65536 + 256) // entries j = -PB_JNEG .. 65536 + 175
 #define PB_SCAN_FRAMES_PER_BLOCK (256 * 8)
-#define PB_VST_SCAN_MIN_WGF 32 // smallest pb_vstage_kernel workgroup the scratch is sized for
 #define PB_CTR_WORDS ((size_t)PB_CTR_SHARDS * PB_CTR_STRIDE) // u64 counter words per sequence
 #define PB_CTR_BYTES (sizeof(unsigned long long) * PB_CTR_WORDS * PB_MAX_SEQUENCES)
 
@@ -84,61 +84,7 @@ static uint64_t scan_tmp_bytes(uint64_t capacity_frames)
 namespace
 {
 
-// Shape overrides for the parity tests and A/B runs (PBGPU_* environment).  They are read in
-// one place, read_opts(): at pbgpu_open into the context (landing, batch and repack options) and at
-// pbgpu_load_sequence into the slot (kernel shapes), so the build path never reads the
-// environment and a loaded sequence's shape is fixed.  Every selectable shape is parity-tested
-// (tests/test_gpu_kernels.py).
-enum pb_kern_force
-{
-    PBO_K_AUTO = 0,
-    PBO_K_GPF,    // PBGPU_KERNEL=gpf: the group-per-frame kernel for frames > 128 B
-    PBO_K_STAGE,  // =stage: pb_stage_kernel
-    PBO_K_VSTAGE, // =vstage: pb_vstage_kernel for packed variable lengths
-    PBO_K_NOPAGE, // =nopage: no pb_xpage_kernel (linear small kernel)
-    PBO_K_LINEAR, // =linear: neither page kernel
-    PBO_K_VPAGE,  // =vpage: the page-shaped packed writer (pb_vrec_kernel + pb_vpage_kernel)
-};
-
-struct pb_opts
-{
-    int kernel = PBO_K_AUTO;
-    uint32_t g = 0;          // PBGPU_G: lanes per frame of the staged / group kernels (8, 16, 32, 64)
-    uint32_t fpw = 0;        // PBGPU_FPW: frames per workgroup of the group kernel / staged window
-    uint32_t wgt = 0;        // PBGPU_WGT=64: one-wave staged workgroups
-    uint32_t wgf = 0;        // PBGPU_WGF: staged frames per workgroup
-    uint32_t stage_kb = 0;   // PBGPU_STAGE_KB: staged window
-    uint32_t small_wgt = 0;  // PBGPU_SMALL_WGT: linear small kernel's workgroup (64 / 128 / 256)
-    uint32_t fst_g = 0, fst_wgf = 0, fst_nbuf = 0; // PBGPU_FST_G / _WGF / _NBUF
-    uint32_t vl_wgf = 0;     // PBGPU_VL_WGF: pb_vline_kernel's own frames per workgroup
-    uint32_t vst_shape = 0;  // PBGPU_VST_SHAPE: pb_vstage_kernel shape bits (pb_kargs.vst_shape)
-    bool vst_scan3 = false;  // PBGPU_VST_SCAN=3pass: pb_vstage_kernel after the 3-pass length scan
-    bool xp_force = false;   // PBGPU_XP_FORCE=1: pb_xpage_kernel for every even length <= 128 B
-    bool xp_static = true;   // PBGPU_XP_STATIC=0: no page kernel for static payloads
-    bool xp_fa64 = false;    // PBGPU_XP_FA64=1: pb_xpage_kernel's 64-bit first-frame path at any size
-    uint32_t xp_wgt = 0;     // PBGPU_XP_WGT: 256 / 512
-    uint32_t xp_np = 0;      // PBGPU_XP_NP: pages per workgroup
-    uint32_t xp_img = 1;     // static-payload ICMP frames: 1 pb_ximg_body in pb_batch_kernel only,
-                             // 2 pb_ximg_kernel for single builds too, 0 never (PBGPU_XP_IMG)
-    bool ctr_atomic = false; // PBGPU_CTR_ATOMIC=1: counts by one atomic per workgroup, no record ring
-    uint32_t ctr_ring = 0;   // PBGPU_CTR_RING: record ring words (small: the fold-when-full path)
-    bool batch = true;       // PBGPU_BATCH=0: pbgpu_build_batch launches every part on its own
-    uint32_t batch_wgt = 512; // PBGPU_BATCH_WGT=256: pb_batch_kernel's 256-thread form
-    bool seq_streams = true; // PBGPU_SEQ_STREAMS=0: span-mode builds all on the context's stream
-    bool land_spin = true;   // PBGPU_LAND_SPIN=0: blocking landing waits
-    bool umem_dma = false;   // PBGPU_UMEM_DMA=1: land through DMA copies, not the mapped scatter
-    bool alloc_vmm = true;   // PBGPU_ALLOC=malloc: frame buffers from hipMalloc (fb_alloc)
-    uint32_t alloc_chunk_mb = 64; // PBGPU_ALLOC_CHUNK_MB: fb_alloc's physical chunk
-    uint32_t land_dma_min = 0xFFFFFFFFu; // PBGPU_LAND_DMA_MIN: fixed frames of at least this many bytes
-                                  // land in registered UMEM by strided DMA instead of the scatter kernel
-                                  // (off by default: 1500 B read 56 vs 52 GB/s landing alone on one box,
-                                  // 43 vs 49 GB/s in bench.py's build + land on another)
-    uint32_t vp_pages_pct = 0; // PBGPU_VP_PAGES_PCT: pb_vpage_kernel's grid as a percentage of the
-                               // expected pages (tests: a short grid, so waves take several pages)
-    uint32_t rp_per = 0;       // PBGPU_RP_PER: pages per workgroup of the five repack writers, 1 to 32
-                               // (tests: several pages per workgroup at outputs of a few MB)
-};
-
+// The PBGPU_* overrides (pb_opts, pb_plan.h), read here alone
 uint32_t opt_u32(const char *name)
 {
     const char *e = getenv(name);
@@ -242,6 +188,7 @@ struct seq_slot
     hipStream_t ctr_last = nullptr; // the stream of the last launch that wrote or folded the ring
     hipEvent_t ctr_ev = nullptr;
     pb_opts opt; // shape overrides, read when the sequence was loaded
+    pb_plan plan; // the build kernel chosen from them (pb_make_plan)
 };
 
 struct timing_pair
@@ -369,39 +316,6 @@ struct pbgpu_ctx
 namespace
 {
 
-uint32_t host_rand_r(uint32_t *seed)
-{
-    uint32_t x = *seed, r;
-    x = x * PB_LCG_A + PB_LCG_C;
-    r = (x >> 16) & 0x7FFu;
-    x = x * PB_LCG_A + PB_LCG_C;
-    r = (r << 10) ^ ((x >> 16) & 0x3FFu);
-    x = x * PB_LCG_A + PB_LCG_C;
-    r = (r << 10) ^ ((x >> 16) & 0x3FFu);
-    *seed = x;
-    return r;
-}
-
-uint32_t host_seed(uint64_t seed_base, uint32_t seq, uint64_t k)
-{
-    uint64_t z = (seed_base ^ (((uint64_t)seq << 48) + k)) + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return (uint32_t)(z ^ (z >> 31));
-}
-
-pb_div make_div(uint32_t d)
-{
-    pb_div v;
-    v.d = d;
-    uint32_t l = 0;
-    while ((1ull << l) < d)
-        ++l;
-    v.sh = 31 + l;
-    v.m = (uint32_t)(((1ull << v.sh) + d - 1) / d);
-    return v;
-}
-
 // jump[j + PB_JNEG] = L^(3(j+1)) as (A, C), j = -PB_JNEG ..
 std::vector<uint2> make_jump_table()
 {
@@ -455,104 +369,6 @@ std::vector<uint32_t> make_orbit_table(uint32_t *total)
     return t;
 }
 
-int str_ieq(const char *a, const char *b)
-{
-    for (; *a && *b; a++, b++)
-        if (tolower((unsigned char)*a) != tolower((unsigned char)*b))
-            return 0;
-    return *a == *b;
-}
-
-void parse_mac(const char *s, uint8_t mac[6])
-{
-    memset(mac, 0, 6);
-    if (s)
-        sscanf(s, "%hhx:%hhx:%hhx:%hhx:%hhx:%hhx", &mac[0], &mac[1], &mac[2], &mac[3], &mac[4], &mac[5]);
-}
-
-// "<ip>/<cidr>" (strtok semantics, as PB-Common rand_ip splits it); invalid
-// ranges take the reference's fail path, 127.0.0.1 (sequence.c:473-482).
-uint2 compile_range(const char *r)
-{
-    uint2 out = make_uint2(0x7F000001u, 0u);
-    if (r == NULL)
-        return out;
-    char *cpy = strdup(r);
-    if (cpy == NULL)
-        return out;
-    char *save = NULL;
-    char *ip = strtok_r(cpy, "/", &save);
-    char *cs = strtok_r(NULL, "/", &save);
-    struct in_addr a;
-    if (ip && cs && inet_aton(ip, &a))
-    {
-        int cidr = atoi(cs);
-        if (cidr >= 0 && cidr <= 32)
-        {
-            uint32_t hm = cidr == 0 ? 0xFFFFFFFFu : (cidr == 32 ? 0u : ((1u << (32 - cidr)) - 1u));
-            out = make_uint2(ntohl(a.s_addr) & ~hm, hm);
-        }
-    }
-    free(cpy);
-    return out;
-}
-
-// exact payload text -> bytes (sequence.c:269-337)
-int compile_exact(const pb_payload_opt_t *po, std::vector<uint8_t> &bytes)
-{
-    std::vector<char> text;
-    if (po->is_file)
-    {
-        FILE *fp = fopen(po->exact, "rb");
-        if (fp)
-        {
-            fseek(fp, 0, SEEK_END);
-            long n = ftell(fp);
-            fseek(fp, 0, SEEK_SET);
-            text.assign(n > 0 ? (size_t)n + 1 : 1, 0);
-            if (n > 0 && fread(text.data(), 1, (size_t)n, fp) != (size_t)n)
-                text.assign(1, 0);
-            fclose(fp);
-        }
-        else
-        {
-            text.assign(1, 0);
-        }
-    }
-    else
-    {
-        size_t n = strlen(po->exact);
-        text.assign(po->exact, po->exact + n + 1);
-    }
-    bytes.clear();
-    if (po->is_string)
-    {
-        size_t n = strlen(text.data());
-        bytes.assign(text.data(), text.data() + n);
-    }
-    else
-    {
-        char *rest = text.data(), *tok;
-        while ((tok = strtok_r(rest, " ", &rest)) != NULL)
-        {
-            unsigned char b = 0;
-            sscanf(tok, "%2hhx", &b);
-            bytes.push_back(b);
-        }
-    }
-    return bytes.size() > PB_MAX_PCKT_LEN ? PBGPU_EINVAL : PBGPU_OK;
-}
-
-uint32_t le_word_sum(const uint8_t *p, size_t n)
-{
-    uint64_t s = 0;
-    for (size_t j = 0; j < n; ++j)
-        s += (uint64_t)p[j] << ((j & 1) * 8);
-    while (s >> 16)
-        s = (s & 0xFFFF) + (s >> 16);
-    return (uint32_t)s;
-}
-
 template <typename T>
 int upload(T **dptr, const T *src, size_t n)
 {
@@ -569,18 +385,6 @@ int upload(T **dptr, const T *src, size_t n)
     HIPCHK(hipMalloc((void **)dptr, n * sizeof(T)));
     HIPCHK(hipMemcpy(*dptr, src, n * sizeof(T), hipMemcpyHostToDevice));
     return PBGPU_OK;
-}
-
-// Dynamic LDS that caps a launch at per_cu workgroups per CU: total LDS per workgroup just over
-// 160 KiB / (per_cu + 1).  (The measured shape: 64-B pages with 41,384 B per workgroup ran 0.29-0.30
-// ms per 2^25 frames, with 46,592 B 0.35 ms like 2 per CU, profiles/r05/ab/xs9.jsonl, so the
-// point just past the next count's boundary is the one to take.)
-#define PB_LDS_PER_CU (160u * 1024u)
-#define PB_XS_WG_PER_CU 3 // pb_xsmall_kernel
-uint32_t lds_cap_pad(uint32_t static_bytes, uint32_t per_cu)
-{
-    const uint32_t target = PB_LDS_PER_CU / (per_cu + 1u) + 512u;
-    return target > static_bytes ? target - static_bytes : 0u;
 }
 
 void slot_free(seq_slot &s)
@@ -878,7 +682,58 @@ void pbgpu_close(pbgpu_ctx *ctx)
     delete ctx;
 }
 
-// sequence_t -> GPU template: thread_hdl() prologue, sequence.c:66-374.
+// the orbit prefix-sum table (pb_orbit_sum, pb_vline_kernel): the 2^24-step
+// walk runs once per process; each context uploads the result
+static int upload_orbit(pbgpu_ctx *ctx)
+{
+    if (ctx->d_orbit != nullptr)
+        return PBGPU_OK;
+    static std::once_flag once;
+    static std::vector<uint32_t> orb;
+    static uint32_t tot = 0;
+    std::call_once(once, [] { orb = make_orbit_table(&tot); });
+    const int rc = upload(&ctx->d_orbit, orb.data(), orb.size());
+    if (rc != PBGPU_OK)
+        return rc;
+    ctx->orbit_tot = tot;
+    return PBGPU_OK;
+}
+
+// pb_ximg_kernel's image (pb_plan.img_np): the stream's first img_np pages, built once, here, with
+// pb_xpage_kernel (counted into a scratch counter array, not the sequence's)
+static int build_image(pbgpu_ctx *ctx, seq_slot &S, pb_kargs &K, const pb_plan &P, const pb_opts &O)
+{
+    const uint32_t np = P.img_np;
+    const uint64_t bytes = (uint64_t)np * PB_XPG;
+    HIPCHK(hipMalloc((void **)&S.d_img, bytes));
+    if (ctx->d_img_ctr == nullptr)
+    {
+        HIPCHK(hipMalloc((void **)&ctx->d_img_ctr, PB_CTR_WORDS * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(ctx->d_img_ctr, 0, PB_CTR_WORDS * sizeof(unsigned long long)));
+    }
+    pb_kargs K2 = K;
+    K2.first_iter = 0;
+    K2.n_frames = (bytes + K.fixed_len - 1) / K.fixed_len + 1;
+    K2.total_bytes = bytes;
+    K2.out = (uint8_t *)S.d_img;
+    K2.counters = ctx->d_img_ctr;
+    K2.ctr_slots = nullptr;
+    pb_plan P2 = P; // the same pages without an image: pb_xpage_kernel
+    P2.kern = PB_KERN_XPAGE;
+    P2.img_solo = false;
+    const pb_kern kern = pb_plan_launch(P2, O, 0, K2);
+    K2.xp_fa_hi = 0;
+    HIPCHK(pbk_launch_build(&K2, kern, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    K.img = S.d_img;
+    K.img_np = np;
+    K.img_div = make_div(np);
+    K.img_solo = P.img_solo;
+    return PBGPU_OK;
+}
+
+// sequence_t -> GPU template: thread_hdl() prologue, sequence.c:66-374 (pb_compile), the build
+// kernel and its shape (pb_make_plan), then the uploads and the device work the plan asks for.
 int pbgpu_load_sequence(pbgpu_ctx *ctx, uint16_t seq_idx, const pb_sequence_t *seq, const uint8_t *src_mac,
                         const uint8_t *dst_mac, const pb_rules_t *rules, uint64_t seed_base)
 {
@@ -917,556 +772,26 @@ int pbgpu_load_sequence(pbgpu_ctx *ctx, uint16_t seq_idx, const pb_sequence_t *s
     }
 
     const pb_opts O = read_opts();
-    pb_rules_t R = {PB_PAYLOAD_STREAM, PB_FOLD_FULL};
-    if (rules)
-        R = *rules;
-    if (seq->ip.dst_ip == NULL) // seq_send refuses it, sequence.c:723-728
-        return PBGPU_EINVAL;
-    if (seq->pl_cnt > PB_MAX_PAYLOADS || seq->ip.range_count > PB_MAX_RANGES)
-        return PBGPU_EINVAL;
-    if (seq->ip.min_ttl > seq->ip.max_ttl || seq->ip.min_id > seq->ip.max_id)
-        return PBGPU_EINVAL; // rand_num modulus <= 0: undefined in the reference
-
-    pb_kargs K;
-    memset(&K, 0, sizeof K);
-    uint8_t t[64];
-    memset(t, 0, sizeof t);
-
-    uint8_t sm[6], dm[6];
-    if (src_mac)
-        memcpy(sm, src_mac, 6);
-    else
-        parse_mac(seq->eth.src_mac, sm);
-    if (dst_mac)
-        memcpy(dm, dst_mac, 6);
-    else
-        parse_mac(seq->eth.dst_mac, dm);
-
-    uint32_t proto = 17;
-    if (seq->ip.protocol && str_ieq(seq->ip.protocol, "tcp"))
-        proto = 6;
-    else if (seq->ip.protocol && str_ieq(seq->ip.protocol, "icmp"))
-        proto = 1;
-    K.proto = proto;
-    K.l4len = proto == 6 ? 20 : 8;
-    K.hl = 14 + 20 + K.l4len;
-    if (proto == 17)
-        K.csum_dw = 10, K.csum_hi = 0; // byte 40
-    else if (proto == 6)
-        K.csum_dw = 12, K.csum_hi = 1; // byte 50
-    else
-        K.csum_dw = 9, K.csum_hi = 0;  // byte 36
-
-    // template, sequence.c:161-258
-    memcpy(t + 0, dm, 6);
-    memcpy(t + 6, sm, 6);
-    t[12] = 0x08;
-    t[13] = 0x00;
-    t[14] = 0x45;
-    t[15] = seq->ip.tos;
-    t[23] = (uint8_t)proto;
-    uint32_t flags = 0;
-    if (seq->ip.min_ttl != seq->ip.max_ttl)
-    {
-        flags |= PBK_RND_TTL;
-        K.ttl_min = seq->ip.min_ttl;
-        K.ttl = make_div((uint32_t)seq->ip.max_ttl - seq->ip.min_ttl + 1);
-    }
-    else
-    {
-        t[22] = seq->ip.max_ttl;
-    }
-    if (seq->ip.min_id != seq->ip.max_id)
-    {
-        flags |= PBK_RND_ID;
-        K.id_min = seq->ip.min_id;
-        K.id = make_div((uint32_t)seq->ip.max_id - seq->ip.min_id + 1);
-    }
-    else
-    {
-        t[18] = (uint8_t)(seq->ip.max_id >> 8);
-        t[19] = (uint8_t)seq->ip.max_id;
-    }
-    std::vector<uint2> ranges;
-    if (seq->ip.src_ip != NULL)
-    {
-        struct in_addr a;
-        memset(&a, 0, sizeof a);
-        inet_aton(seq->ip.src_ip, &a);
-        memcpy(t + 26, &a.s_addr, 4);
-    }
-    else if (seq->ip.range_count > 0)
-    {
-        flags |= PBK_RND_SADDR;
-        for (int r = 0; r < seq->ip.range_count; ++r)
-            ranges.push_back(compile_range(seq->ip.ranges[r]));
-        K.rng = make_div(seq->ip.range_count);
-    }
-    else
-    {
-        const uint32_t lo = htonl(0x7F000001u); // sequence.c:484-490
-        memcpy(t + 26, &lo, 4);
-    }
-    {
-        struct in_addr a;
-        memset(&a, 0, sizeof a);
-        inet_aton(seq->ip.dst_ip, &a);
-        memcpy(t + 30, &a.s_addr, 4);
-    }
-    if (proto == 17 || proto == 6)
-    {
-        const uint16_t sp = proto == 17 ? seq->udp.src_port : seq->tcp.src_port;
-        const uint16_t dp = proto == 17 ? seq->udp.dst_port : seq->tcp.dst_port;
-        if (sp)
-            t[34] = (uint8_t)(sp >> 8), t[35] = (uint8_t)sp;
-        else
-            flags |= PBK_RND_SPORT;
-        if (dp)
-            t[36] = (uint8_t)(dp >> 8), t[37] = (uint8_t)dp;
-        else
-            flags |= PBK_RND_DPORT;
-        K.port = make_div(65535);
-        flags |= PBK_PSEUDO;
-    }
-    if (proto == 6)
-    {
-        t[46] = 5 << 4;
-        t[47] = (uint8_t)((seq->tcp.fin & 1) | (seq->tcp.syn & 1) << 1 | (seq->tcp.rst & 1) << 2 |
-                          (seq->tcp.psh & 1) << 3 | (seq->tcp.ack & 1) << 4 | (seq->tcp.urg & 1) << 5 |
-                          (seq->tcp.ece & 1) << 6 | (seq->tcp.cwr & 1) << 7);
-    }
-    else if (proto == 1)
-    {
-        t[34] = seq->icmp.type;
-        t[35] = seq->icmp.code;
-    }
-    if (seq->ip.csum)
-        flags |= PBK_IP_CSUM;
-    if (seq->l4_csum)
-        flags |= PBK_L4_CSUM;
-    if (R.iph_fold == PB_FOLD_SINGLE)
-        flags |= PBK_IPH_SINGLE;
-    if (R.payload_rule == PB_PAYLOAD_LITERAL)
-        flags |= PBK_LITERAL;
-    memcpy(K.tmpl, t, 64);
-
-    // payloads, sequence.c:264-374
-    std::vector<pb_pl> pls;
-    std::vector<uint8_t> blob(96, 0); // >= 80 B of zeros before every static payload
-    uint16_t dl_setup[PB_MAX_PAYLOADS];
-    memset(dl_setup, 0, sizeof dl_setup);
-    uint32_t sseed = host_seed(seed_base, seq_idx, PB_STATIC_SEED_K); // quirk B2
-    int n_random = 0;
-    uint32_t max_random = 0;
-    for (int i = 0; i < seq->pl_cnt; ++i)
-    {
-        const pb_payload_opt_t *po = &seq->pls[i];
-        pb_pl P;
-        memset(&P, 0, sizeof P);
-        std::vector<uint8_t> bytes;
-        bool is_static = po->is_static;
-        if (po->exact != NULL)
-        {
-            is_static = true;
-            int rc = compile_exact(po, bytes);
-            if (rc)
-                return rc;
-        }
-        else if (po->is_static && po->max_len > 0)
-        {
-            if (po->min_len > po->max_len)
-                return PBGPU_EINVAL;
-            uint32_t s2 = sseed;
-            const uint32_t len = po->min_len + host_rand_r(&s2) % ((uint32_t)po->max_len - po->min_len + 1);
-            dl_setup[i] = (uint16_t)len;
-            bytes.assign(len, 0);
-            if (R.payload_rule == PB_PAYLOAD_LITERAL)
-            {
-                // the shadowed index runs while j < data_len[j], which may pass the payload's
-                // own length: those draws still advance the seed, their bytes are not sent
-                for (uint32_t j = 0; j < PB_MAX_PAYLOADS && j < dl_setup[j]; ++j)
-                {
-                    const uint8_t v = (uint8_t)host_rand_r(&sseed);
-                    if (j < len)
-                        bytes[j] = v;
-                }
-            }
-            else
-            {
-                for (uint32_t j = 0; j < len; ++j)
-                    bytes[j] = (uint8_t)host_rand_r(&sseed);
-            }
-        }
-        if (is_static)
-        {
-            dl_setup[i] = (uint16_t)bytes.size();
-            P.random = 0;
-            P.slen = (uint32_t)bytes.size();
-            P.blob_off = (uint32_t)blob.size();
-            P.ssum = le_word_sum(bytes.data(), bytes.size());
-            blob.insert(blob.end(), bytes.begin(), bytes.end());
-            blob.insert(blob.end(), 96 + 16 - (bytes.size() & 15), 0); // >= 96 B zero pad, 16-B aligned
-        }
-        else if (po->max_len > 0)
-        {
-            if (po->min_len > po->max_len)
-                return PBGPU_EINVAL;
-            P.random = 1;
-            P.min_len = po->min_len;
-            P.len = make_div((uint32_t)po->max_len - po->min_len + 1);
-            ++n_random;
-            if (po->max_len > max_random)
-                max_random = po->max_len;
-        }
-        else
-        {
-            P.random = 0; // non-static, max_len 0: empty payload (sequence.c:557-560)
-            P.slen = 0;
-            P.blob_off = 16 + 64;
-        }
-        if (K.hl + (P.random ? po->max_len : P.slen) > PB_MAX_PCKT_LEN)
-            return PBGPU_EINVAL;
-        pls.push_back(P);
-    }
-    if (pls.empty()) // sequence.c:364-374
-    {
-        pb_pl P;
-        memset(&P, 0, sizeof P);
-        P.blob_off = 16 + 64;
-        pls.push_back(P);
-    }
-    // literal rule with several payloads (quirk B8, sequence.c:349 / 552): a random payload's
-    // loop `for (u16 i = 0; i < data_len[i]; i++)` reads the other payloads' data_len[]
-    // entries, so it draws until the first j with data_len[j] <= j.  Entries j > i hold
-    // their setup values (declared rule, as the oracle); their part of the stop index is
-    // fixed per payload here, the part of j <= i is found per iteration in pb_payload.
-    std::vector<uint32_t> lit_stop(pls.size());
-    for (size_t i = 0; i < pls.size(); ++i)
-    {
-        uint32_t j = (uint32_t)i + 1;
-        while (j < PB_MAX_PAYLOADS && j < dl_setup[j])
-            ++j;
-        lit_stop[i] = j;
-    }
-    if ((flags & PBK_LITERAL) || max_random <= 64)
-        flags |= PBK_SUM_IN_A;
-
-    K.pl_cnt = (uint32_t)pls.size();
-    K.pl0 = pls[0];
-    K.flags = flags;
-    K.seed_base = seed_base;
-    K.seq = seq_idx;
-
-    // frame lengths
-    uint32_t minf = 0xFFFFFFFFu, maxf = 0;
-    for (const pb_pl &P : pls)
-    {
-        const uint32_t lo = K.hl + (P.random ? P.min_len : P.slen);
-        const uint32_t hi = K.hl + (P.random ? P.min_len + P.len.d - 1 : P.slen);
-        minf = lo < minf ? lo : minf;
-        maxf = hi > maxf ? hi : maxf;
-    }
-    S.min_flen = minf;
-    S.max_flen = maxf;
-    S.fpi = (uint32_t)pls.size();
-    const bool fixed = pls.size() == 1 && (!pls[0].random || pls[0].len.d == 1);
-    K.fixed_len = fixed ? minf : 0;
-    if (fixed)
-        K.flen = make_div(minf);
-    // small fixed frames: one lane per frame (pb_small_kernel)
-    if (fixed && pls.size() == 1 && minf <= 128)
-    {
-        K.small_ndw = minf <= 64 ? 16 : 32;
-        {
-            // the linear small kernel's frames per workgroup: 64 for even lengths (their 64-frame
-            // regions end on 128-B lines), measured 2.5% faster than 256 on the 98-B ICMP frame
-            // (0.649 vs 0.666 ms per 2^25 frames; 128: 0.666; profiles/r02/ab/small_wgt_icmp98.txt);
-            // odd lengths keep 256 (line-aligned regions).  PBGPU_SMALL_WGT = 64 / 128 / 256 overrides
-            const uint32_t w = O.small_wgt ? O.small_wgt : (minf % 2 == 0 ? 64u : 256u);
-            K.small_wgt = (w == 64 || w == 128) ? w : 0u;
-        }
-        const bool xp_force = O.xp_force; // pb_xpage_kernel for any even length
-        if (4096 % minf == 0 && minf == 4 * K.small_ndw && !xp_force) // pages of whole frames: pb_xsmall_kernel (64 / 128 B)
-        {
-            while ((minf << K.xs_fp_shift) < 4096)
-                ++K.xs_fp_shift;
-            K.xs_np = 256 >> K.xs_fp_shift;
-            // one wave per page is fastest with few waves per CU (profiles/r05/ab/xs9.jsonl):
-            // 64-B frames 0.297-0.303 ms per 2^25 at 3 workgroups per CU, 0.323-0.329 uncapped
-            // (measured for 64-B frames only; 128-B pages keep the uncapped launch)
-            if (K.xs_fp_shift == 6)
-                K.lds_pad = lds_cap_pad(K.xs_np * PB_XPG, PB_XS_WG_PER_CU);
-        }
-        else if ((xp_force && minf % 2 == 0) ||
-                 (O.kernel != PBO_K_NOPAGE && minf % 2 == 0 && minf >= 52 && minf <= 128 &&
-                  (minf % 4 == 0 && minf <= 64 ? true : !pls[0].random && O.xp_static)))
-        {
-            // XCD-owned 4 KiB pages for frames cut at the page edges (pb_xpage_kernel): one slot
-            // per frame touching a page, 512-thread workgroups (one pass of slots): lengths of
-            // 52-64 B that are multiples of 4, and static payloads at every even length of 52-128 B
-            // that does not divide 4096.  Round 4 (profiles/r04/ab/len_*.jsonl, xp_*.jsonl): static
-            // payloads 5-16% faster than the linear small kernel at 54-126 B, 13% at the 98-B ICMP
-            // frame (0.474-0.481 vs 0.549-0.552 ms, 4 buffers), and the rate does not depend on the
-            // buffer's placement; random payloads over 64 B or of 2 mod 4 lose
-            // 20-30% (each straddling frame's payload generated twice); 60-B TCP 512 vs 256
-            // threads 0.296-0.298 vs 0.300-0.302 ms.  Pages per workgroup: 9 for lengths of 2 mod 4 (98 B:
-            // 0.474-0.481 ms vs 0.496-0.501 at 7, 0.489-0.491 at 11, 0.574-0.577 at 5), 7 otherwise
-            // (68 / 100 / 120 B: 7 faster than 9), at most the slots of one pass.
-            K.xp = 1;
-            K.xp_fpp = (4096 + minf - 1) / minf + 1;
-            K.xp_div = make_div(K.xp_fpp);
-            K.xp_inv = 1.0 / (double)minf;
-            K.xp_wgt = O.xp_wgt == 256 ? 256 : 512;
-            const uint32_t want = minf % 4 == 2 ? 9u : 7u;
-            K.xs_np = std::max<uint32_t>(1, std::min<uint32_t>(want, 2 * PB_WG / K.xp_fpp));
-            if (O.xp_np && O.xp_np * K.xp_fpp <= 2 * PB_WG) // at most two frame slots per 256 lanes
-                K.xs_np = O.xp_np;
-        }
-        if (!pls[0].random)
-        {
-            const uint32_t p0 = (K.hl - 2) / 4;
-            for (uint32_t j = 0; j < pls[0].slen; ++j)
-            {
-                const uint32_t pos = K.hl + j;
-                K.stail[pos / 4 - p0] |= (uint32_t)blob[pls[0].blob_off + j] << (8 * (pos % 4));
-            }
-        }
-    }
-    {
-        if (!K.small_ndw)
-        {
-            // lanes per frame (measured, profiles/r01/gsweep): equal-length frames take
-            // the group size that wastes the fewest lanes on the frame's chunk count,
-            // preferring 32 (1500-B frames: 4.2 TB/s at G=32, 3.5 at 8, 2.9 at 64);
-            // packed variable-length frames take 8 (configs[2]: 3.35 TB/s at 8, 2.7
-            // at 32).  PBGPU_G overrides (8, 16, 32, 64) for experiments.
-            if (K.fixed_len)
-            {
-                const uint32_t nch = (minf + 15) / 16 + 1;
-                double best = -1;
-                for (uint32_t gg : {32u, 16u, 8u})
-                {
-                    const double util = (double)nch / (gg * ((nch + gg - 1) / gg));
-                    if (util > best + 0.05)
-                        best = util, K.gpf_g = gg;
-                }
-            }
-            else
-            {
-                K.gpf_g = 8;
-            }
-            if (O.g)
-                K.gpf_g = O.g;
-            K.gpf_rmode = n_random == (int)pls.size() ? 1 : (n_random == 0 ? 0 : 2);
-            const uint32_t ngw = PB_WG / K.gpf_g; // frames in flight per workgroup
-            uint32_t fpw = O.fpw ? O.fpw : PB_WG;
-            fpw = fpw < ngw ? ngw : (fpw > PB_WG ? PB_WG : fpw);
-            K.gpf_fpw = fpw / ngw * ngw;
-
-            // staged kernel (frames assembled in LDS, each window of the output written
-            // as one contiguous run).  Lanes per frame G: the smallest of the group
-            // sizes that waste the fewest lanes on a frame's payload chunks whose
-            // 256 / G frames in flight span at most 26 KiB.  Fixed-length windows hold
-            // k * 256 / G frames (~20 KiB); variable-length windows PBGPU_STAGE_KB
-            // (default 24) KiB.  Measured (profiles/r01/stage): 1500-B frames 5.1 TB/s
-            // at G = 16, 16 frames per window (group-per-frame: 4.1); 1024-B 5.2 at 16
-            // frames; 9000-B 5.2 at G = 64.
-            // variable-length frames: staged with G = 8 (configs[2], 2^23 frames: 1.81-1.86 ms
-            // vs 2.01 on the group-per-frame kernel, since B writes payload chunks
-            // unmasked); PBGPU_KERNEL=gpf forces the group-per-frame kernel.  A flat B
-            // (one list of the window's payload chunks, checksums from LCG-cycle prefix
-            // sums) measured slower: 2.1-2.5 ms
-            const bool gpf_only = O.kernel == PBO_K_GPF;
-            const uint32_t avg = (minf + maxf) / 2;
-            const uint32_t npc = (avg - K.hl) / 16 + 2;
-            double umax = 0;
-            for (uint32_t gg : {8u, 16u, 32u, 64u})
-                umax = std::max(umax, (double)npc / (gg * ((npc + gg - 1) / gg)));
-            uint32_t sg = 64;
-            for (uint32_t gg : {8u, 16u, 32u, 64u})
-                if ((double)npc / (gg * ((npc + gg - 1) / gg)) >= umax - 0.02 && (PB_WG / gg) * avg <= 26 * 1024)
-                {
-                    sg = gg;
-                    break;
-                }
-            if (!K.fixed_len)
-                sg = 8;
-            if (O.g)
-                sg = O.g;
-            const uint32_t wgt = O.wgt == 64 ? 64u : (uint32_t)PB_WG;
-            uint32_t wgf = K.fixed_len ? 64 : 128;
-            if (O.wgf && O.wgf <= PB_WG)
-                wgf = O.wgf;
-            wgf = std::min(wgf, wgt);
-            uint32_t win, sbytes;
-            if (K.fixed_len)
-            {
-                const uint32_t ngw2 = std::max(1u, wgt / sg);
-                uint32_t fw = ngw2 * std::max(1u, (20u * 1024 * wgt / PB_WG) / (ngw2 * maxf));
-                if (O.stage_kb)
-                    fw = std::max(1u, O.stage_kb * 1024 / maxf);
-                if (O.fpw)
-                    fw = O.fpw;
-                const uint32_t fit = (uint32_t)((64 * 1024 - 48 - PB_STAGE_LDS(std::max(wgf, fw))) / maxf);
-                fw = std::max(1u, std::min(fw, fit)); // the stage must fit 64 KiB of LDS
-                win = fw * maxf;
-                sbytes = (win + 30 + 15) / 16 * 16;
-            }
-            else
-            {
-                // 24 KiB windows.  pb_vstage_kernel (configs[2], 2^25 frames, profiles/r02/ab/hv2_*):
-                // 6.37 ms at 24 KiB, 6.68 at 16, 7.34 at 28 (3 workgroups per CU) since it keeps
-                // only 9 header dwords per frame in LDS; with 16-dword images 16 KiB was best
-                const uint32_t skb = O.stage_kb ? O.stage_kb : 24;
-                sbytes = (skb * 1024 + 15) / 16 * 16;
-                if (sbytes < 2 * maxf + 48)
-                    sbytes = (2 * maxf + 48 + 15) / 16 * 16;
-                win = sbytes - maxf - 32;
-            }
-            if (K.fixed_len)
-            {
-                const uint32_t fw = win / maxf; // whole windows per workgroup
-                wgf = fw > wgt ? wgt : std::min<uint32_t>(wgt / fw * fw, fw * ((wgf + fw - 1) / fw));
-            }
-            else if (!O.wgf)
-                wgf = std::min<uint32_t>(wgt, std::max(wgf, win / minf + 1));
-            if (!gpf_only && sbytes + PB_STAGE_LDS(wgf) <= 64 * 1024)
-            {
-                K.gpf_g = sg;
-                K.stage_win = win;
-                K.stage_wgf = wgf;
-                K.stage_wgt = wgt;
-                K.stage_bytes = sbytes;
-                // every payload random, stream rule: pb_vstage_kernel (no header pass, no
-                // serial byte loops in phase A; configs[2] 1.74 vs 1.87 ms per 2^23 frames at
-                // the best window of each); PBGPU_KERNEL=stage keeps pb_stage_kernel
-                if (K.gpf_rmode == 1 && !(flags & PBK_LITERAL) && wgt == PB_WG && O.kernel != PBO_K_STAGE &&
-                    sbytes + PB_VST_LDS(wgf) <= 64 * 1024)
-                {
-                    K.vst = 1;
-                    K.vst_shape = O.vst_shape;
-                    // phase A has one lane per slot (ghosts + own frames): as many own frames as
-                    // lanes allow, which also spreads the per-workgroup work over the most windows
-                    // (configs[2], 2^25 frames: 6.37 ms at 240-252 vs 6.44 at 218 and 6.50 at 200;
-                    // profiles/r02/ab/wf24*)
-                    // (as many as still leave 4 workgroups per CU when the window's frames fit)
-                    K.stage_wgf = std::min<uint32_t>(K.stage_wgf, PB_WG - PB_VST_GHOSTS);
-                    if (!O.wgf && !K.fixed_len)
-                    {
-                        uint32_t best = PB_WG - PB_VST_GHOSTS;
-                        while (best > K.stage_wgf && K.stage_bytes + PB_VST_LDS(best) > 160 * 1024 / 4)
-                            --best;
-                        K.stage_wgf = best;
-                    }
-                }
-            }
-            // fixed-length staged kernel (pb_fstage_kernel): lengths > 128 B that are a
-            // multiple of 4, every payload random, stream rule.  One stage buffer, then two;
-            // G = the smallest of 16, 32, 64 whose stage of 256 / G frames fits 64 KiB with
-            // the per-frame records; 64 frames per workgroup.  Measured on 1500-B frames
-            // (profiles/r01/fstage): 1 buffer G = 16 2.12 ms per 2^23 frames, 2 buffers 2.20,
-            // G = 32 2.21, G = 64 2.35, 32 / 128 frames per workgroup 2.15 / 2.20;
-            // pb_stage_kernel 2.29.  PBGPU_KERNEL=stage / gpf keep the older kernels,
-            // PBGPU_FST_G, PBGPU_FST_WGF, PBGPU_FST_NBUF override the shape.
-            const bool fst_ok = K.fixed_len && minf > 128 && minf % 4 == 0 && K.gpf_rmode == 1 &&
-                                !(flags & PBK_LITERAL) && !gpf_only && O.kernel != PBO_K_STAGE;
-            // packed variable lengths, every payload random, stream rule, payloads of >= 32 B:
-            // pb_vline_kernel (no LDS stage).  ICMP type 0 / code 0 is left to
-            // pb_vstage_kernel: its header word sum can be 0, where the orbit sums cannot tell a
-            // zero payload sum from 0xFFFF.  PBGPU_KERNEL=vstage keeps pb_vstage_kernel.
-            const bool icmp00 = proto == 1 && t[34] == 0 && t[35] == 0;
-            // the orbit prefix-sum table (pb_orbit_sum, pb_vline_kernel): the 2^24-step
-            // walk runs once per process; each context uploads the result
-            auto need_orbit = [&]() -> int {
-                if (ctx->d_orbit == nullptr)
-                {
-                    static std::once_flag once;
-                    static std::vector<uint32_t> orb;
-                    static uint32_t tot = 0;
-                    std::call_once(once, [] { orb = make_orbit_table(&tot); });
-                    const int rc2 = upload(&ctx->d_orbit, orb.data(), orb.size());
-                    if (rc2 != PBGPU_OK)
-                        return rc2;
-                    ctx->orbit_tot = tot;
-                }
-                K.orbit = ctx->d_orbit;
-                K.orbit_tot = ctx->orbit_tot;
-                return PBGPU_OK;
-            };
-            if (!K.fixed_len && K.gpf_rmode == 1 && !(flags & PBK_LITERAL) && !gpf_only && minf >= K.hl + 32 &&
-                maxf <= 4096 && !icmp00 && O.kernel != PBO_K_VSTAGE && O.kernel != PBO_K_STAGE)
-            {
-                const uint32_t nsp = K.hl == 54 ? 5u : 4u;
-                uint32_t wf = O.vl_wgf ? O.vl_wgf : PB_WG - PB_VST_GHOSTS;
-                wf = std::max(32u, std::min<uint32_t>(wf, PB_WG - PB_VST_GHOSTS));
-                uint32_t nl48 = 0, nlines = 0;
-                for (;; wf -= 4)
-                {
-                    const uint64_t rmax = (uint64_t)wf * maxf + 256; // own frames + the line before the first
-                    nl48 = (maxf + 31) / 16 + 1;
-                    nlines = (uint32_t)(rmax / 128 + 2);
-                    if (PB_VL_LDS(wf, nsp, nl48, nlines) <= 40 * 1024 || wf <= 32) // >= 4 workgroups per CU
-                        break;
-                }
-                const int orc = need_orbit();
-                if (orc != PBGPU_OK)
-                    return orc;
-                K.vl = 1;
-                K.vl_wgf = wf;
-                K.vl_nl48 = nl48;
-                K.vl_nlines = nlines;
-                // PBGPU_KERNEL=vpage, one payload: the page-shaped writer (pb_vrec_kernel +
-                // pb_vpage_kernel).  Bit-exact and immune to the buffer placement
-                // that slows pb_vline_kernel, but 7.1 vs 4.2 ms per 2^25 configs[2] frames: each
-                // page's frame setup runs one lane per frame (~6 of 64 lanes), 3.4 G VALU
-                // instructions per launch against 2.0 G (profiles/r06/vpage/)
-                const uint32_t nfp = (4096 + minf - 1) / minf + 1;
-                if (pls.size() == 1 && nfp <= 64 && O.kernel == PBO_K_VPAGE)
-                {
-                    K.vl = 0;
-                    K.vp = 1;
-                    K.vp_nfp = nfp;
-                }
-            }
-            if (fst_ok)
-            {
-                const uint32_t eg = O.fst_g, ew = O.fst_wgf, en = O.fst_nbuf;
-                for (uint32_t nb : {1u, 2u})
-                {
-                    if (en && nb != en)
-                        continue;
-                    for (uint32_t gg : {16u, 32u, 64u})
-                    {
-                        if ((eg && gg != eg) || K.hl / 4 >= gg)
-                            continue;
-                        const uint32_t ngw = PB_WG / gg;
-                        uint32_t fw = ew ? ew : 64;
-                        fw = std::max(ngw, std::min<uint32_t>(PB_WG, fw / ngw * ngw));
-                        const uint32_t sb = (ngw * minf + 15) / 16 * 16;
-                        if ((size_t)nb * sb + PB_FST_LDS(fw) <= 64 * 1024)
-                        {
-                            K.fst_g = gg;
-                            K.fst_wgf = fw;
-                            K.fst_sb = sb;
-                            K.fst_nbuf = nb;
-                            break;
-                        }
-                    }
-                    if (K.fst_g)
-                        break;
-                }
-            }
-        }
-    }
-    int rc;
-    if ((rc = upload(&S.d_ranges, ranges.data(), ranges.size())) != PBGPU_OK)
+    pb_compiled C;
+    int rc = pb_compile(seq_idx, seq, src_mac, dst_mac, rules, seed_base, &C);
+    if (rc != PBGPU_OK)
         return rc;
-    if ((rc = upload(&S.d_pls, pls.data(), pls.size())) != PBGPU_OK)
+    const pb_plan P = pb_make_plan(C, O);
+    pb_kargs &K = C.K;
+    if (P.orbit) // (first, as the allocations have always been ordered)
+    {
+        if ((rc = upload_orbit(ctx)) != PBGPU_OK)
+            return rc;
+        K.orbit = ctx->d_orbit;
+        K.orbit_tot = ctx->orbit_tot;
+    }
+    if ((rc = upload(&S.d_ranges, C.ranges.data(), C.ranges.size())) != PBGPU_OK)
         return rc;
-    if ((rc = upload(&S.d_lit_stop, lit_stop.data(), lit_stop.size())) != PBGPU_OK)
+    if ((rc = upload(&S.d_pls, C.pls.data(), C.pls.size())) != PBGPU_OK)
         return rc;
-    blob.insert(blob.end(), 64, 0);
-    if ((rc = upload(&S.d_blob, blob.data(), blob.size())) != PBGPU_OK)
+    if ((rc = upload(&S.d_lit_stop, C.lit_stop.data(), C.lit_stop.size())) != PBGPU_OK)
+        return rc;
+    if ((rc = upload(&S.d_blob, C.blob.data(), C.blob.size())) != PBGPU_OK)
         return rc;
     K.ranges = S.d_ranges;
     K.pls = S.d_pls;
@@ -1478,50 +803,14 @@ int pbgpu_load_sequence(pbgpu_ctx *ctx, uint16_t seq_idx, const pb_sequence_t *s
     K.m16 = ctx->d_m16;
     K.dlog12 = ctx->d_dlog12;
     K.counters = ctx->d_counters + PB_CTR_WORDS * seq_idx;
-    // pb_ximg_kernel (static-payload ICMP frames): only IPv4 ID, TTL, checksum and
-    // source address vary per frame, so the stream's bytes repeat every img_np = flen / gcd(flen,
-    // 4096) pages outside those fields.  Build its first img_np pages once, here, with
-    // pb_xpage_kernel (counted into a scratch counter array, not the sequence's)
-    if (K.xp && K.proto == 1 && !pls[0].random && K.fixed_len % 2 == 0 && O.xp_img && !O.xp_force &&
-        O.kernel == PBO_K_AUTO &&
-        !(K.flags & (PBK_RND_SPORT | PBK_RND_DPORT)))
-    {
-        uint32_t g = K.fixed_len, a = PB_XPG;
-        while (a)
-        {
-            const uint32_t t = g % a;
-            g = a;
-            a = t;
-        }
-        const uint32_t np = K.fixed_len / g;
-        const uint64_t bytes = (uint64_t)np * PB_XPG;
-        HIPCHK(hipMalloc((void **)&S.d_img, bytes));
-        if (ctx->d_img_ctr == nullptr)
-        {
-            HIPCHK(hipMalloc((void **)&ctx->d_img_ctr, PB_CTR_WORDS * sizeof(unsigned long long)));
-            HIPCHK(hipMemset(ctx->d_img_ctr, 0, PB_CTR_WORDS * sizeof(unsigned long long)));
-        }
-        pb_kargs K2 = K;
-        K2.img = nullptr;
-        K2.first_iter = 0;
-        K2.n_frames = (bytes + K.fixed_len - 1) / K.fixed_len + 1;
-        K2.total_bytes = bytes;
-        K2.out = (uint8_t *)S.d_img;
-        K2.counters = ctx->d_img_ctr;
-        K2.ctr_slots = nullptr;
-        K2.xs_nch = np;
-        K2.xs_full = np / (8 * K2.xs_np) * 8;
-        K2.xs_grid = K2.xs_full + (np - K2.xs_full * K2.xs_np + K2.xs_np - 1) / K2.xs_np;
-        K2.xp_fa_hi = 0;
-        HIPCHK(pbk_launch_build(&K2, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        K.img = S.d_img;
-        K.img_np = np;
-        K.img_div = make_div(np);
-        K.img_solo = O.xp_img == 2;
-    }
+    if (P.img_np && (rc = build_image(ctx, S, K, P, O)) != PBGPU_OK)
+        return rc;
     S.K = K;
+    S.fpi = C.fpi;
+    S.min_flen = C.min_flen;
+    S.max_flen = C.max_flen;
     S.opt = O;
+    S.plan = P;
     S.loaded = true;
     return PBGPU_OK;
 }
@@ -2062,8 +1351,9 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
         K.vblk_sum = nullptr;
         K.vblk_l2 = nullptr;
         K.offsets_w = nullptr;
-        const uint32_t wgf = K.vp ? (uint32_t)PB_WG : (K.vl ? K.vl_wgf : K.stage_wgf);
-        if (K.vl || K.vp || (K.vst && K.stage_wgf >= PB_VST_SCAN_MIN_WGF && !S.opt.vst_scan3))
+        const bool vp = S.plan.kern == PB_KERN_VPAGE, vl = S.plan.kern == PB_KERN_VLINE;
+        const uint32_t wgf = pb_plan_len_wgf(S.plan, S.opt, K);
+        if (wgf)
         {
             // pb_vline_kernel / pb_vstage_kernel: per-workgroup length sums, their scan, offsets
             // written by the build
@@ -2076,7 +1366,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
             K.vblk_sum = bsum;
             K.vblk_l2 = l2;
             K.offsets_w = out->offsets;
-            if (K.vp)
+            if (vp)
             {
                 // the record pass's records (8 B per frame) and page table (8 B per page of the
                 // buffer's capacity); the page grid covers the longest stream these frames can make
@@ -2104,7 +1394,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
                     return PBGPU_ENOSPC;
                 K.vp_grid = (uint32_t)((pages + ppg - 1) / ppg * 8);
             }
-            if (K.vl || K.vp)
+            if (vl || vp)
             {
                 // 4 B per frame and 8 B per region instead of 8 B per frame
                 // (each checked on its own: a failed second allocation must not leave the pair
@@ -2125,37 +1415,9 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
             HIPCHK(pbk_launch_lengths(&K, (unsigned long long *)out->scan_tmp, (uint32_t)nblocks, out->offsets, st));
         }
     }
-    K.xs_grid = 0;
-    if (bp && K.small_ndw && K.xs_np && !K.xp) // pb_batch_kernel's 64-B part at the batch's block size
-        K.xs_np = bp->wgt >> K.xs_fp_shift;
-    const bool img = K.img && (bp || K.img_solo); // pb_ximg_kernel / the batch's ICMP part
-    if (!img)
-        K.img = nullptr;
-    else // one page per wave
-        K.xs_np = (bp ? bp->wgt : PB_WG) / 64;
-    if (K.small_ndw && K.xs_np && ((uintptr_t)K.out & 4095u) == 0 && S.opt.kernel != PBO_K_LINEAR)
-    {
-        // XCD-owned 4 KiB pages, xs_np per workgroup: pb_xsmall_kernel (one wave per page) takes
-        // groups of 8 workgroups (pages past the stream are skipped);
-        // pb_xpage_kernel and the batch's 64-B part take full groups of 8, then the tail pages in order
-        const uint64_t nch = (K.total_bytes + 4095) / 4096;
-        if (nch < 0x7FFFFFFFull)
-        {
-            K.xs_nch = (uint32_t)nch;
-            const uint32_t np = K.xs_np;
-            K.xs_full = (uint32_t)(nch / (8 * np) * 8);
-            if ((K.xp || (bp && K.small_ndw)) && !K.img)
-                K.xs_grid = K.xs_full + (uint32_t)((nch - (uint64_t)K.xs_full * np + np - 1) / np);
-            else
-                K.xs_grid = (uint32_t)((nch + 8ull * np - 1) / (8ull * np) * 8);
-            // (PBGPU_XP_FA64=1: the 64-bit path at any size, so the tests reach it)
-            K.xp_fa_hi = K.xp && ((uint64_t)nch * (4096 % K.fixed_len) >= (1ull << 31) || S.opt.xp_fa64);
-        }
-    }
-    // the load-time occupancy cap (lds_pad) belongs to pb_xsmall_kernel's page launch alone: the
-    // linear fallback (an output not 4-KiB aligned, PBGPU_KERNEL=linear) keeps its own occupancy
-    if (K.xs_grid == 0)
-        K.lds_pad = 0;
+    // the kernel this build launches (the small family falls back to pb_small_kernel on an output
+    // not 4-KiB aligned) and its page arithmetic
+    const pb_kern kern = pb_plan_launch(S.plan, S.opt, bp ? bp->wgt : 0u, K);
     timing_pair tp = {nullptr, nullptr};
     int rc = PBGPU_OK;
     // this launch's per-workgroup count records (pb_count): the next words of the sequence's
@@ -2167,7 +1429,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
     if (!S.opt.ctr_atomic)
     {
         const uint64_t pairs = K.fixed_len ? 1 : 2;
-        words = (uint64_t)pbk_build_grid(&K) * pairs;
+        words = (uint64_t)pbk_build_grid(&K, kern) * pairs;
         if (S.ctr_pairs != pairs || S.ctr_used + words > S.ctr_cap)
         {
             if ((rc = ctr_fold(ctx, seq_idx, st)) != PBGPU_OK)
@@ -2238,7 +1500,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
             }
             ctx->seq_dirty[si] = true;
         }
-        HIPCHK_UNDO(pbk_launch_build(&K, st));
+        HIPCHK_UNDO(pbk_launch_build(&K, kern, st));
         ++ctx->span_n;
         return mark_built(ctx, out, st);
     }
@@ -2248,7 +1510,7 @@ static int build_impl(pbgpu_ctx *ctx, uint16_t seq_idx, uint64_t first_iter, uin
         return rc;
     }
     HIPCHK_UNDO(hipEventRecord(tp.a, ctx->stream));
-    HIPCHK_UNDO(pbk_launch_build(&K, ctx->stream));
+    HIPCHK_UNDO(pbk_launch_build(&K, kern, ctx->stream));
 #undef HIPCHK_UNDO
     // launched: its records will be written; a failing end event drops only this timing
     HIPCHK(hipEventRecord(tp.b, ctx->stream));
@@ -3985,32 +3247,24 @@ int pbgpu_kernel_name(pbgpu_ctx *ctx, uint16_t seq_idx, char *buf, size_t n)
     const seq_slot &S = ctx->seqs[seq_idx];
     if (!S.loaded)
         return PBGPU_ENOENT;
-    const pb_kargs &K = S.K;
-    if (K.vp)
-        snprintf(buf, n, "pb_vpage_kernel<%u, %u> (after pb_vrec_kernel<%u, %u>)", K.hl,
-                 (K.flags & PBK_L4_CSUM) ? 1u : 0u, K.hl, (K.flags & PBK_L4_CSUM) ? 1u : 0u);
-    else if (K.vl)
-        snprintf(buf, n, "pb_vline_kernel<%u, %u>", K.hl, (K.flags & PBK_L4_CSUM) ? 1u : 0u);
-    else if (K.fst_g)
-        snprintf(buf, n, "pb_fstage_kernel<%u, %u>", K.fst_g, (K.flags & PBK_L4_CSUM) ? 1u : 0u);
-    else if (K.stage_win && K.vst)
-        snprintf(buf, n, "pb_vstage_kernel<%u, %u>", K.gpf_g, (K.flags & PBK_L4_CSUM) ? 1u : 0u);
-    else if (K.stage_win)
-        snprintf(buf, n, "pb_stage_kernel<%u, %u>", K.gpf_g, K.gpf_rmode);
-    else if (K.gpf_g)
-        snprintf(buf, n, "pb_gpf_kernel<%u, %u>", K.gpf_g, K.gpf_rmode);
-    else if (K.xs_np && K.img && K.img_solo && S.opt.kernel != PBO_K_LINEAR)
-        snprintf(buf, n, "pb_ximg_kernel<%u>", (uint32_t)PB_WG);
-    else if (K.xs_np && K.xp && S.opt.kernel != PBO_K_LINEAR)
-        snprintf(buf, n, "pb_xpage_kernel<%u, %u, %s, %u, %s>%s", K.small_ndw, K.proto, K.pl0.random ? "true" : "false",
-                 K.xp_wgt, K.fixed_len % 4 == 0 ? "true" : "false",
-                 K.img ? " (in pbgpu_build_batch: pb_ximg_body)" : "");
-    else if (K.xs_np && S.opt.kernel != PBO_K_LINEAR)
-        snprintf(buf, n, "pb_xsmall_kernel<%u, %u, %s, %u>", K.small_ndw, K.proto, K.pl0.random ? "true" : "false",
-                 (uint32_t)PB_WG);
-    else
-        snprintf(buf, n, "pb_small_kernel<%u, %u, %s, %u, %u>", K.small_ndw, K.proto, K.pl0.random ? "true" : "false",
-                 K.small_wgt ? K.small_wgt : (uint32_t)PB_WG, K.fixed_len % 4 == 2 ? 2u : 0u);
+    pb_plan_name(S.plan, S.K, buf, n);
+    return PBGPU_OK;
+}
+
+// Test hook: what pbgpu_load_sequence would choose for this sequence under the present PBGPU_*
+// environment, as one line (pb_plan_describe); no context and no device
+int pbgpu_plan_describe(uint16_t seq_idx, const pb_sequence_t *seq, const pb_rules_t *rules, uint64_t seed_base,
+                        char *buf, size_t n)
+{
+    if (seq == NULL || seq_idx >= PB_MAX_SEQUENCES || buf == NULL || n == 0)
+        return PBGPU_EINVAL;
+    const pb_opts O = read_opts();
+    pb_compiled C;
+    const int rc = pb_compile(seq_idx, seq, NULL, NULL, rules, seed_base, &C);
+    if (rc != PBGPU_OK)
+        return rc;
+    const pb_plan P = pb_make_plan(C, O);
+    pb_plan_describe(C, P, O, pbk_batch_kind(&C.K), buf, n);
     return PBGPU_OK;
 }
 

@@ -7,7 +7,7 @@
 // sequence.c:552-555, in 24-bit LCG arithmetic), the L4 checksum
 // (csum_tcpudp_magic / icmp_csum, sequence.c:563-594) and tot_len + the IPv4
 // checksum (sequence.c:596-602), written packed into HBM.  Kernel by frame
-// shape (selection in pbgpu_load_sequence):
+// shape (selection in pb_make_plan, pb_plan.cpp):
 //   pb_xsmall_kernel / pb_xpage_kernel / pb_small_kernel   frames <= 128 B, one lane per frame
 //   pb_fstage_kernel                                      fixed length > 128 B, random payload
 //   pb_vstage_kernel                                      packed variable length, random payload
@@ -16,7 +16,10 @@
 // The template, CIDR table pointers and divisors arrive as kernel arguments
 // (scalar registers); no inter-workgroup communication; no atomics to HBM
 // except two counter adds per launch.
+#include <type_traits>
+
 #include "pb_device.h"
+#include "pb_plan.h" // pb_kern: the launch's kernel
 
 #define PB_SCAN_ITEMS 8    // frames per thread in the length scan kernels
 
@@ -3352,86 +3355,75 @@ static size_t pb_small_tile_bytes(uint32_t wgt, uint32_t flen)
     return (((size_t)wgt * flen + 15) & ~(size_t)15) + 32;
 }
 
-// pb_small_kernel: workgroup b builds frames [wgt b, wgt b + wgt)
-template <int NDW, int PROTO, bool RANDOM, int AL>
-static void pbk_launch_linear(const pb_kargs *K, hipStream_t st)
+// A runtime value as a template argument: f(std::integral_constant<int, V>) for the first V of
+// the list that equals v, for the last V when none does
+template <int V0, int... Vs, typename F>
+static void pb_with(uint32_t v, F &&f)
 {
-    const uint32_t wgt = K->small_wgt ? K->small_wgt : PB_WG;
-    const dim3 g((uint32_t)((K->n_frames + wgt - 1) / wgt));
-    const size_t lds = pb_small_tile_bytes(wgt, K->fixed_len) + K->lds_pad;
-    if (wgt == 64)
-        hipLaunchKernelGGL((pb_small_kernel<NDW, PROTO, RANDOM, 64, AL>), g, dim3(64), lds, st, *K);
-    else if (wgt == 128)
-        hipLaunchKernelGGL((pb_small_kernel<NDW, PROTO, RANDOM, 128, AL>), g, dim3(128), lds, st, *K);
+    if constexpr (sizeof...(Vs) == 0)
+        f(std::integral_constant<int, V0>{});
+    else if (v == (uint32_t)V0)
+        f(std::integral_constant<int, V0>{});
     else
-        hipLaunchKernelGGL((pb_small_kernel<NDW, PROTO, RANDOM, PB_WG, AL>), g, dim3(PB_WG), lds, st, *K);
+        pb_with<Vs...>(v, f);
 }
 
-template <int NDW, int PROTO>
-static void pbk_launch_small_p(const pb_kargs *K, uint32_t grid, hipStream_t st)
+template <typename F>
+static void pb_with_bool(bool v, F &&f)
 {
-    if (K->xs_grid && K->img && K->img_solo)
+    if (v)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
+// The small family: pb_small_kernel (workgroup b builds frames [wgt b, wgt b + wgt)) and its page
+// forms, by frame dwords, protocol and payload kind
+static void pbk_launch_small(const pb_kargs *K, pb_kern kern, hipStream_t st)
+{
+    if (kern == PB_KERN_XIMG)
     {
         hipLaunchKernelGGL((pb_ximg_kernel<PB_WG>), dim3(K->xs_grid), dim3(PB_WG), K->lds_pad, st, *K);
         return;
     }
-    if (K->xs_grid && K->xp)
-    {
-        const size_t lds = (size_t)K->xs_np * PB_XREG + K->lds_pad;
-        const bool w512 = K->xp_wgt == 512;
-        const dim3 g(K->xs_grid);
-        if (K->fixed_len % 4 == 0)
-        {
-            if (K->pl0.random && w512)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, true, 512>), g, dim3(512), lds, st, *K);
-            else if (K->pl0.random)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, true, PB_WG>), g, dim3(PB_WG), lds, st, *K);
-            else if (w512)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, false, 512>), g, dim3(512), lds, st, *K);
-            else
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, false, PB_WG>), g, dim3(PB_WG), lds, st, *K);
-        }
-        else // 2 mod 4: static-payload frames (98-B ICMP); any even length under PBGPU_XP_FORCE
-        {
-            if (K->pl0.random && w512)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, true, 512, false>), g, dim3(512), lds, st, *K);
-            else if (K->pl0.random)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, true, PB_WG, false>), g, dim3(PB_WG), lds, st, *K);
-            else if (w512)
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, false, 512, false>), g, dim3(512), lds, st, *K);
-            else
-                hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, false, PB_WG, false>), g, dim3(PB_WG), lds, st, *K);
-        }
-    }
-    else if (K->xs_grid)
-    {
-        if (K->pl0.random)
-            hipLaunchKernelGGL((pb_xsmall_kernel<NDW, PROTO, true>), dim3(K->xs_grid), dim3(PB_WG), K->lds_pad, st, *K);
-        else
-            hipLaunchKernelGGL((pb_xsmall_kernel<NDW, PROTO, false>), dim3(K->xs_grid), dim3(PB_WG), K->lds_pad, st, *K);
-    }
-    else if (K->fixed_len % 4 == 2) // 98-B ICMP, 106-B UDP: only the 2-mod-4 tile writes compiled in
-    {
-        if (K->pl0.random)
-            pbk_launch_linear<NDW, PROTO, true, 2>(K, st);
-        else
-            pbk_launch_linear<NDW, PROTO, false, 2>(K, st);
-    }
-    else if (K->pl0.random)
-        pbk_launch_linear<NDW, PROTO, true, 0>(K, st);
-    else
-        pbk_launch_linear<NDW, PROTO, false, 0>(K, st);
-}
-
-template <int NDW>
-static void pbk_launch_small(const pb_kargs *K, uint32_t grid, hipStream_t st)
-{
-    if (K->proto == 17)
-        pbk_launch_small_p<NDW, 17>(K, grid, st);
-    else if (K->proto == 6)
-        pbk_launch_small_p<NDW, 6>(K, grid, st);
-    else
-        pbk_launch_small_p<NDW, 1>(K, grid, st);
+    pb_with<16, 32>(K->small_ndw, [&](auto ndw) {
+        pb_with<17, 6, 1>(K->proto, [&](auto proto) {
+            pb_with_bool(K->pl0.random != 0, [&](auto random) {
+                constexpr int NDW = decltype(ndw)::value, PROTO = decltype(proto)::value;
+                constexpr bool RANDOM = decltype(random)::value;
+                if (kern == PB_KERN_XPAGE)
+                {
+                    const size_t lds = (size_t)K->xs_np * PB_XREG + K->lds_pad;
+                    // (not a multiple of 4: 2 mod 4, static-payload frames (98-B ICMP); any even length
+                    // under PBGPU_XP_FORCE)
+                    pb_with<512, PB_WG>(K->xp_wgt, [&](auto wgt) {
+                        pb_with_bool(K->fixed_len % 4 == 0, [&](auto a4) {
+                            constexpr int WGT = decltype(wgt)::value;
+                            hipLaunchKernelGGL((pb_xpage_kernel<NDW, PROTO, RANDOM, WGT, decltype(a4)::value>),
+                                               dim3(K->xs_grid), dim3(WGT), lds, st, *K);
+                        });
+                    });
+                }
+                else if (kern == PB_KERN_XSMALL)
+                    hipLaunchKernelGGL((pb_xsmall_kernel<NDW, PROTO, RANDOM>), dim3(K->xs_grid), dim3(PB_WG),
+                                       K->lds_pad, st, *K);
+                else
+                {
+                    const uint32_t nw = K->small_wgt ? K->small_wgt : PB_WG;
+                    const dim3 g((uint32_t)((K->n_frames + nw - 1) / nw));
+                    const size_t lds = pb_small_tile_bytes(nw, K->fixed_len) + K->lds_pad;
+                    // (2 mod 4: 98-B ICMP, 106-B UDP: only the 2-mod-4 tile writes compiled in)
+                    pb_with<64, 128, PB_WG>(nw, [&](auto wgt) {
+                        pb_with<2, 0>(K->fixed_len % 4 == 2 ? 2u : 0u, [&](auto al) {
+                            constexpr int WGT = decltype(wgt)::value;
+                            hipLaunchKernelGGL((pb_small_kernel<NDW, PROTO, RANDOM, WGT, decltype(al)::value>), g,
+                                               dim3(WGT), lds, st, *K);
+                        });
+                    });
+                }
+            });
+        });
+    });
 }
 
 // pb_batch_kernel's part kind of a loaded sequence's kargs (0: no fused form)
@@ -3475,200 +3467,111 @@ extern "C" hipError_t pbk_launch_batch(const pb_kargs *Ks, uint32_t wgt, hipStre
     return hipGetLastError();
 }
 
-// The workgroups pbk_launch_build launches for K (pb_count's records per launch)
-extern "C" uint32_t pbk_build_grid(const pb_kargs *K)
+// The workgroups pbk_launch_build launches for K (pb_count's records per launch): the page
+// kernels' own grid, else the frames over the kernel's frames per workgroup
+extern "C" uint32_t pbk_build_grid(const pb_kargs *K, pb_kern kern)
 {
-    const uint64_t n = K->n_frames;
     uint64_t per = 0;
-    if (K->vp)
-        return K->vp_grid;
-    if (K->vl)
-        per = K->vl_wgf;
-    else if (K->fst_g)
-        per = K->fst_wgf;
-    else if (K->gpf_g && !K->stage_win)
-        per = K->gpf_fpw;
-    else if (K->stage_win)
-        per = K->stage_wgf;
-    else if (K->small_ndw && K->xs_grid)
-        return K->xs_grid;
-    else if (K->small_ndw)
-        per = K->small_wgt ? K->small_wgt : PB_WG;
-    return per ? (uint32_t)((n + per - 1) / per) : 0u;
+    switch (kern)
+    {
+    case PB_KERN_VPAGE: return K->vp_grid;
+    case PB_KERN_XSMALL:
+    case PB_KERN_XPAGE:
+    case PB_KERN_XIMG: return K->xs_grid;
+    case PB_KERN_VLINE: per = K->vl_wgf; break;
+    case PB_KERN_FSTAGE: per = K->fst_wgf; break;
+    case PB_KERN_GPF: per = K->gpf_fpw; break;
+    case PB_KERN_STAGE:
+    case PB_KERN_VSTAGE: per = K->stage_wgf; break;
+    case PB_KERN_SMALL: per = K->small_wgt ? K->small_wgt : PB_WG; break;
+    case PB_KERN_NONE: break;
+    }
+    return per ? (uint32_t)((K->n_frames + per - 1) / per) : 0u;
 }
 
-extern "C" hipError_t pbk_launch_build(const pb_kargs *K, hipStream_t st)
+// kern: the launch's kernel (pb_plan_launch), its shape in K
+extern "C" hipError_t pbk_launch_build(const pb_kargs *K, pb_kern kern, hipStream_t st)
 {
-    if (K->vp)
+    const uint32_t grid = pbk_build_grid(K, kern);
+    const bool l4csum = (K->flags & PBK_L4_CSUM) != 0;
+    switch (kern)
+    {
+    case PB_KERN_VPAGE:
     {
         // the record pass, then the pages (both are the build: one timed span)
         const uint32_t rgrid = (uint32_t)((K->n_frames + PB_WG - 1) / PB_WG);
-        const bool l4 = (K->flags & PBK_L4_CSUM) != 0;
-        const uint32_t nsp = K->hl == 54 ? 5u : 4u;
-        const size_t lds = PB_VP_LDS(K->vp_nfp, nsp, 4);
-#define PB_VP(HH, LL)                                                                                       \
-    do                                                                                                      \
-    {                                                                                                       \
-        hipLaunchKernelGGL((pb_vrec_kernel<HH, LL>), dim3(rgrid), dim3(PB_WG), 0, st, *K);                  \
-        hipLaunchKernelGGL((pb_vpage_kernel<HH, LL>), dim3(K->vp_grid), dim3(PB_WG), lds, st, *K);          \
-    } while (0)
-        if (K->hl == 54)
-        {
-            if (l4)
-                PB_VP(54, true);
-            else
-                PB_VP(54, false);
-        }
-        else if (l4)
-            PB_VP(42, true);
-        else
-            PB_VP(42, false);
-#undef PB_VP
+        const size_t lds = PB_VP_LDS(K->vp_nfp, K->hl == 54 ? 5u : 4u, 4);
+        pb_with<54, 42>(K->hl, [&](auto hl) {
+            pb_with_bool(l4csum, [&](auto l4) {
+                constexpr int HL = decltype(hl)::value;
+                constexpr bool L4 = decltype(l4)::value;
+                hipLaunchKernelGGL((pb_vrec_kernel<HL, L4>), dim3(rgrid), dim3(PB_WG), 0, st, *K);
+                hipLaunchKernelGGL((pb_vpage_kernel<HL, L4>), dim3(grid), dim3(PB_WG), lds, st, *K);
+            });
+        });
+        break;
     }
-    else if (K->vl)
+    case PB_KERN_VLINE:
     {
-        const uint32_t grid = (uint32_t)((K->n_frames + K->vl_wgf - 1) / K->vl_wgf);
         const size_t lds = PB_VL_LDS(K->vl_wgf, K->hl == 54 ? 5 : 4, K->vl_nl48, K->vl_nlines) + K->lds_pad;
-        const bool l4 = (K->flags & PBK_L4_CSUM) != 0;
-        if (K->hl == 54)
-        {
-            if (l4)
-                hipLaunchKernelGGL((pb_vline_kernel<54, true>), dim3(grid), dim3(PB_WG), lds, st, *K);
-            else
-                hipLaunchKernelGGL((pb_vline_kernel<54, false>), dim3(grid), dim3(PB_WG), lds, st, *K);
-        }
-        else
-        {
-            if (l4)
-                hipLaunchKernelGGL((pb_vline_kernel<42, true>), dim3(grid), dim3(PB_WG), lds, st, *K);
-            else
-                hipLaunchKernelGGL((pb_vline_kernel<42, false>), dim3(grid), dim3(PB_WG), lds, st, *K);
-        }
+        pb_with<54, 42>(K->hl, [&](auto hl) {
+            pb_with_bool(l4csum, [&](auto l4) {
+                hipLaunchKernelGGL((pb_vline_kernel<decltype(hl)::value, decltype(l4)::value>), dim3(grid),
+                                   dim3(PB_WG), lds, st, *K);
+            });
+        });
+        break;
     }
-    else if (K->fst_g)
+    case PB_KERN_FSTAGE:
     {
-        const uint32_t grid = (uint32_t)((K->n_frames + K->fst_wgf - 1) / K->fst_wgf);
         const size_t lds = (size_t)K->fst_nbuf * K->fst_sb + PB_FST_LDS(K->fst_wgf) + K->lds_pad;
-        const bool l4 = (K->flags & PBK_L4_CSUM) != 0;
-#define PB_FST(GG)                                                                                        \
-    do                                                                                                    \
-    {                                                                                                     \
-        if (l4)                                                                                           \
-            hipLaunchKernelGGL((pb_fstage_kernel<GG, true>), dim3(grid), dim3(PB_WG), lds, st, *K);      \
-        else                                                                                              \
-            hipLaunchKernelGGL((pb_fstage_kernel<GG, false>), dim3(grid), dim3(PB_WG), lds, st, *K);     \
-    } while (0)
-        if (K->fst_g == 16)
-            PB_FST(16);
-        else if (K->fst_g == 32)
-            PB_FST(32);
-        else
-            PB_FST(64);
-#undef PB_FST
+        pb_with<16, 32, 64>(K->fst_g, [&](auto g) {
+            pb_with_bool(l4csum, [&](auto l4) {
+                hipLaunchKernelGGL((pb_fstage_kernel<decltype(g)::value, decltype(l4)::value>), dim3(grid),
+                                   dim3(PB_WG), lds, st, *K);
+            });
+        });
+        break;
     }
-    else if (K->gpf_g && !K->stage_win)
+    case PB_KERN_GPF:
+        pb_with<8, 16, 32, 64>(K->gpf_g, [&](auto g) {
+            pb_with<1, 0, 2>(K->gpf_rmode, [&](auto rm) {
+                hipLaunchKernelGGL((pb_gpf_kernel<decltype(g)::value, decltype(rm)::value>), dim3(grid), dim3(PB_WG),
+                                   0, st, *K);
+            });
+        });
+        break;
+    case PB_KERN_VSTAGE:
     {
-        const uint32_t grid = (uint32_t)((K->n_frames + K->gpf_fpw - 1) / K->gpf_fpw);
-        const uint32_t rm = K->gpf_rmode;
-#define PB_GPF(GG, RM) hipLaunchKernelGGL((pb_gpf_kernel<GG, RM>), dim3(grid), dim3(PB_WG), 0, st, *K)
-#define PB_GPF_RM(GG)      \
-    if (rm == 1)           \
-        PB_GPF(GG, 1);     \
-    else if (rm == 0)      \
-        PB_GPF(GG, 0);     \
-    else                   \
-        PB_GPF(GG, 2)
-        if (K->gpf_g == 8)
-        {
-            PB_GPF_RM(8);
-        }
-        else if (K->gpf_g == 16)
-        {
-            PB_GPF_RM(16);
-        }
-        else if (K->gpf_g == 32)
-        {
-            PB_GPF_RM(32);
-        }
-        else
-        {
-            PB_GPF_RM(64);
-        }
-#undef PB_GPF_RM
-#undef PB_GPF
-    }
-    else if (K->stage_win && K->vst)
-    {
-        const uint32_t grid = (uint32_t)((K->n_frames + K->stage_wgf - 1) / K->stage_wgf);
         const size_t lds = K->stage_bytes + PB_VST_LDS(K->stage_wgf) + K->lds_pad;
-        const bool l4 = (K->flags & PBK_L4_CSUM) != 0;
-#define PB_VST(GG)                                                                                    \
-    do                                                                                                \
-    {                                                                                                 \
-        if (l4)                                                                                       \
-            hipLaunchKernelGGL((pb_vstage_kernel<GG, true>), dim3(grid), dim3(PB_WG), lds, st, *K);  \
-        else                                                                                          \
-            hipLaunchKernelGGL((pb_vstage_kernel<GG, false>), dim3(grid), dim3(PB_WG), lds, st, *K); \
-    } while (0)
-        if (K->gpf_g == 8)
-            PB_VST(8);
-        else if (K->gpf_g == 16)
-            PB_VST(16);
-        else if (K->gpf_g == 32)
-            PB_VST(32);
-        else
-            PB_VST(64);
-#undef PB_VST
+        pb_with<8, 16, 32, 64>(K->gpf_g, [&](auto g) {
+            pb_with_bool(l4csum, [&](auto l4) {
+                hipLaunchKernelGGL((pb_vstage_kernel<decltype(g)::value, decltype(l4)::value>), dim3(grid),
+                                   dim3(PB_WG), lds, st, *K);
+            });
+        });
+        break;
     }
-    else if (K->stage_win)
+    case PB_KERN_STAGE:
     {
-        const uint32_t grid = (uint32_t)((K->n_frames + K->stage_wgf - 1) / K->stage_wgf);
         const size_t lds = K->stage_bytes + PB_STAGE_LDS(K->stage_wgf) + K->lds_pad;
-        const uint32_t rm = K->gpf_rmode;
-#define PB_STG(GG, RM)                                                                                     \
-    do                                                                                                     \
-    {                                                                                                      \
-        if (K->stage_wgt == 64)                                                                            \
-            hipLaunchKernelGGL((pb_stage_kernel<GG, RM, 64>), dim3(grid), dim3(64), lds, st, *K);          \
-        else                                                                                               \
-            hipLaunchKernelGGL((pb_stage_kernel<GG, RM, PB_WG>), dim3(grid), dim3(PB_WG), lds, st, *K);    \
-    } while (0)
-#define PB_STG_RM(GG)      \
-    if (rm == 1)           \
-        PB_STG(GG, 1);     \
-    else if (rm == 0)      \
-        PB_STG(GG, 0);     \
-    else                   \
-        PB_STG(GG, 2)
-        if (K->gpf_g == 8)
-        {
-            PB_STG_RM(8);
-        }
-        else if (K->gpf_g == 16)
-        {
-            PB_STG_RM(16);
-        }
-        else if (K->gpf_g == 32)
-        {
-            PB_STG_RM(32);
-        }
-        else
-        {
-            PB_STG_RM(64);
-        }
-#undef PB_STG_RM
-#undef PB_STG
+        pb_with<8, 16, 32, 64>(K->gpf_g, [&](auto g) {
+            pb_with<1, 0, 2>(K->gpf_rmode, [&](auto rm) {
+                pb_with<64, PB_WG>(K->stage_wgt, [&](auto wgt) {
+                    constexpr int WGT = decltype(wgt)::value;
+                    hipLaunchKernelGGL((pb_stage_kernel<decltype(g)::value, decltype(rm)::value, WGT>), dim3(grid),
+                                       dim3(WGT), lds, st, *K);
+                });
+            });
+        });
+        break;
     }
-    else if (K->small_ndw)
-    {
-        const uint32_t grid = (uint32_t)((K->n_frames + PB_WG - 1) / PB_WG);
-        if (K->small_ndw == 16)
-            pbk_launch_small<16>(K, grid, st);
-        else
-            pbk_launch_small<32>(K, grid, st);
+    case PB_KERN_SMALL:
+    case PB_KERN_XSMALL:
+    case PB_KERN_XPAGE:
+    case PB_KERN_XIMG: pbk_launch_small(K, kern, st); break;
+    default: return hipErrorInvalidValue; // pb_make_plan selects one of the kernels above for every sequence
     }
-    else
-        return hipErrorInvalidValue; // pbgpu_load_sequence selects one of the kernels above for every sequence
     return hipGetLastError();
 }
 

@@ -566,6 +566,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pbgpu_verify_wire": (C.c_int, [P, FP, C.c_uint64, C.c_uint64, C.POINTER(WireOpts), C.POINTER(WireResult), P]),
         "pbgpu_abi_size": (C.c_size_t, [C.c_int]),
         "pbgpu_kernel_name": (C.c_int, [P, C.c_uint16, C.c_char_p, C.c_size_t]),
+        "pbgpu_plan_describe": (C.c_int, [C.c_uint16, C.POINTER(SequenceT), C.POINTER(Rules), C.c_uint64, C.c_char_p,
+                                          C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         if path != LIB_PATH and not hasattr(lib, name):
@@ -984,6 +986,17 @@ class GpuContext:
             return fb.frames()
         finally:
             fb.free()
+
+
+def plan_describe(idx: int, seq: Sequence, seed_base: int, payload_rule: int = PAYLOAD_STREAM,
+                  iph_fold: int = FOLD_FULL) -> str:
+    """What load_sequence would choose for seq under the present PBGPU_* environment, as one line:
+    the kernel's name, " | ", then key=value pairs.  Needs no GPU and no context."""
+    rules = Rules(payload_rule, iph_fold)
+    buf = C.create_string_buffer(1024)
+    _check(load_library().pbgpu_plan_describe(idx, C.byref(seq.c), C.byref(rules), C.c_uint64(seed_base), buf,
+                                              len(buf)), "plan_describe")
+    return buf.value.decode()
 
 
 def device_count() -> int:

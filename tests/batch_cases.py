@@ -2,7 +2,8 @@
 of each part, and the table of cases tests/test_gpu_batch_family.py runs; no GPU here
 (tests/test_batch_cases_cpu.py checks this file against itself and the oracle).
 
-The rule, restated from the comments of pbgpu_load_sequence and pbk_batch_kind.  A sequence has a
+The rule, restated from the comments of the planner (pb_make_plan) and pbk_batch_kind, and held
+against the planner itself in tests/test_batch_cases_cpu.py.  A sequence has a
 fused form when it has one payload and one frame length of at most 128 B, was not loaded under
 PBGPU_BATCH=0 or PBGPU_KERNEL=linear, and is one of
   kind 1  UDP, random payload, 64 B, on the whole-frame page kernel (so not under PBGPU_XP_FORCE=1,
@@ -91,9 +92,13 @@ def batch_kind(cfg, env):
 def has_image(cfg, env):
     """A kind-3 sequence's part runs pb_ximg_body: the image is built at load unless PBGPU_XP_IMG=0,
     PBGPU_XP_FORCE=1 or PBGPU_KERNEL names one of its kernels (any other value is the default).
-    (The load also skips it for random ports, which an ICMP sequence cannot have.)"""
-    return (batch_kind(cfg, env) == 3 and env.get("PBGPU_XP_IMG") != "0" and env.get("PBGPU_XP_FORCE") != "1"
-            and env.get("PBGPU_KERNEL") not in KERNEL_CHOICES)
+    (The load also skips it for random ports, which an ICMP sequence cannot have.)  The load builds
+    it for every static-payload ICMP sequence on the cut-frame page kernel, so also at the multiples
+    of 4 (100 B), which have no fused form and use it only under PBGPU_XP_IMG=2, and under
+    PBGPU_BATCH=0 (the planner, held against this in tests/test_batch_cases_cpu.py)."""
+    static = page_kernel(cfg, env) == "cut" and payload_form(cfg["payloads"][0])[0]
+    return (static and cfg["ip"]["protocol"] == "icmp" and env.get("PBGPU_XP_IMG") != "0"
+            and env.get("PBGPU_XP_FORCE") != "1" and env.get("PBGPU_KERNEL") not in KERNEL_CHOICES)
 
 
 # ------------------------------------------------------------------ page arithmetic

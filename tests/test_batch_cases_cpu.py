@@ -132,6 +132,35 @@ def test_count_classes_do_what_they_claim():
     assert {tuple(b.order) for c in bc.CASES for b in bc.batches(c)} == set(bc.ORDERS)
 
 
+def test_rule_matches_the_planner():
+    """The rule restated in batch_cases.py against the library's planner (pbgpu_plan_describe, no
+    GPU): the kind, the image, the page kernel and the page parameters of every part of every case
+    and of every near miss."""
+    import plan_cases as plc
+
+    family = {None: ("pb_small_kernel",), "whole": ("pb_xsmall_kernel",), "cut": ("pb_xpage_kernel", "pb_ximg_kernel")}
+    parts = [(c.id, cfg, env) for c in bc.CASES for cfg, env in c.parts]
+    parts += [(name, cfg, env) for name, _, cfg, env in bc.NEAR_MISSES]
+    assert len(parts) == 3 * 64 + 9
+    for what, cfg, env in parts:
+        assert "PBGPU_BATCH" not in env
+        name, f = plc.parse(plc.describe(cfg, env))
+        assert f["batch"] == bc.batch_kind(cfg, env), what
+        assert (f["img_np"] > 0) == bc.has_image(cfg, env), what
+        pk = bc.page_kernel(cfg, env)
+        flen = bc.frame_length(cfg)
+        if flen is None:  # two payloads: no small kernel at all
+            assert pk is None and not name.startswith(("pb_small", "pb_xsmall", "pb_xpage", "pb_ximg")), what
+            continue
+        assert name.startswith(family[pk]), (what, name)
+        if pk == "whole":
+            assert (1 << f["xs_fp_shift"], f["xs_np"]) == bc.page_params(flen, 256, False, whole=True)[:2], what
+        elif pk == "cut":
+            assert (f["xp_fpp"], f["xs_np"]) == bc.page_params(flen, 512, False)[:2], what
+            if f["img_np"]:
+                assert f["img_np"] == bc.page_params(flen, 512, True)[2], what
+
+
 def test_oracle_builds_every_case_config():
     done = set()
     for case in bc.CASES:

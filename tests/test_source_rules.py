@@ -34,12 +34,12 @@ def _functions(src):
 
 
 def test_environment_is_read_only_by_the_options_reader():
-    src = open(os.path.join(CSRC, "pbgpu.cpp")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("pbgpu.cpp", "pb_plan.h", "pb_plan.cpp"))
     fns = _functions(src)
     readers = {n for n, body in fns.items() if "getenv" in body}
     assert readers <= {"opt_u32", "opt_is", "read_opts", "verbose"}, readers
     callers = {n for n, body in fns.items() if re.search(r"\bread_opts\s*\(\s*\)", body) and n != "read_opts"}
-    assert callers == {"pbgpu_open", "pbgpu_load_sequence"}, callers
+    assert callers == {"pbgpu_open", "pbgpu_load_sequence", "pbgpu_plan_describe"}, callers
     for hot in ("build_impl", "build_check", "pbgpu_build", "pbgpu_build_batch", "batch_fusable"):
         assert hot in fns, hot
         assert "getenv" not in fns[hot] and "read_opts" not in fns[hot], hot
@@ -49,6 +49,7 @@ def test_losing_variants_are_not_compiled_in():
     k = open(os.path.join(CSRC, "pbgpu_kernels.hip")).read()
     h = open(os.path.join(CSRC, "pb_device.h")).read()
     c = open(os.path.join(CSRC, "pbgpu.cpp")).read()
+    p = open(os.path.join(CSRC, "pb_plan.h")).read() + open(os.path.join(CSRC, "pb_plan.cpp")).read()
     gone = ["PB_COUNT", "PB_RANGE_LDS", "PB_TIMING", "PB_XS_XREMAP", "PB_SMALL_XREMAP", "PB_FST_XREMAP",
             "PB_VST_XREMAP", "PB_VL_LATE", "PB_VL_SPLIT", "PB_VL_IMGW", "PB_VL_MT", "PB_ORB_LOG12", "PB_ORB_BIDIR",
             "PB_SMALL_DYN", "PB_XS_NT", "PB_SX_NT", "PB_FS_NT", "PB_VL_NT", "xcd_rot", "store_flip", "fst_dbg",
@@ -57,7 +58,7 @@ def test_losing_variants_are_not_compiled_in():
             # round 6: the page writer's 512-thread and pooled-setup forms (measured, removed)
             "PBGPU_VP_WGT", "PBGPU_VP_POOL", "vp_wgt", "vp_pool", "pb_vpool_kernel"]
     for name in gone:
-        for label, text in (("kernels", k), ("pb_device.h", h), ("pbgpu.cpp", c)):
+        for label, text in (("kernels", k), ("pb_device.h", h), ("pbgpu.cpp", c), ("pb_plan", p)):
             assert re.search(r"\b" + re.escape(name) + (r"\b" if name[-1].isalnum() else ""), text) is None, \
                 (name, label)
 

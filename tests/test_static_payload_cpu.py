@@ -213,6 +213,21 @@ def test_gpu_case_tables_name_every_static_kernel_form():
     assert not any(", true" in n or n.endswith(", 1>") for n in names)  # no random-only kernel among them
 
 
+def test_gpu_case_tables_name_the_planned_kernels():
+    """Every case's expected kernel name in static_cases against the library's planner
+    (pbgpu_plan_describe, no GPU): the name the GPU file will assert is the one the load chooses."""
+    import plan_cases as plc
+
+    want = plc.static_expectations()
+    cases = {c[0]: c for c in plc.cases() if c[0] in want}
+    assert len(cases) == len(want) == len(sc.small_cases()) + len(sc.stage_cases()) + len(sc.gpf_cases()) + \
+        len(sc.mixed_cases())
+    for cid, (name, exact) in want.items():
+        _, cfg, env, rule, fold = cases[cid]
+        got = plc.parse(plc.describe(cfg, env, rule, fold))[0]
+        assert got == name if exact else got.startswith(name), (cid, got, name)
+
+
 def test_gpu_case_tables_follow_test_gpu_kernels():
     """The small-frame lengths and counts and the forced stage shapes are test_gpu_kernels' own."""
     import test_gpu_kernels as tk
