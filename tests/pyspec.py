@@ -54,25 +54,36 @@ def inet_aton(s):
         return None
 
 
-def parse_range(r):
-    if r is None:
-        return None
-    toks = [t for t in r.split("/") if t]
-    if r.startswith("/") or len(toks) < 2:
-        return None
-    ip = inet_aton(toks[0])
-    if ip is None:
-        return None
+def atoi(s):
+    """glibc atoi: (int)strtol(s, NULL, 10): white space skipped, an optional sign, decimal digits;
+    no digit gives 0; the value is held to a long's range, then cut to an int's 32 bits."""
+    s = s.lstrip(" \t\n\v\f\r")
     digits = ""
-    for ch in toks[1].lstrip():
-        if ch.isdigit() or (not digits and ch in "+-"):
+    for ch in s:
+        if ch in "0123456789" or (not digits and ch in "+-"):
             digits += ch
         else:
             break
     try:
-        cidr = int(digits)
+        v = int(digits)
     except ValueError:
-        cidr = 0
+        return 0
+    v = max(-2**63, min(2**63 - 1, v)) & MASK32
+    return v - 2**32 if v >> 31 else v
+
+
+def parse_range(r):
+    """"<ip>/<cidr>" as strtok_r(.., "/") splits it: empty tokens do not exist, so slashes in
+    front are skipped ("/8/24" is ip "8", cidr 24) and a third token is ignored."""
+    if r is None:
+        return None
+    toks = [t for t in r.split("/") if t]
+    if len(toks) < 2:
+        return None
+    ip = inet_aton(toks[0])
+    if ip is None:
+        return None
+    cidr = atoi(toks[1])
     if cidr < 0 or cidr > 32:
         return None
     hm = MASK32 if cidr == 0 else ((1 << (32 - cidr)) - 1)
