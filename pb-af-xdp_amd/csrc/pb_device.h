@@ -224,7 +224,9 @@ struct pb_kargs
 #endif
 #define PB_VS_SLACK 64u
 #define PB_VS_BF_MAX 512u  // ... and the most frames per window
-#define PB_VREC_DW 8       // a workgroup's record: {bad, short, ip, tot_len | l4, 0, first bad lo, hi} (two 16-B stores)
+// a workgroup's record of N counts: the counts, the first bad index (lo, hi), zeros up to whole 16-B stores
+#define PB_REC_DW(N) (((N) + 2 + 3) & ~3)
+#define PB_VREC_DW PB_REC_DW(5) // bad, short, ip, tot_len, l4
 struct pb_vargs
 {
     const uint8_t *data;     // frames->data (16-B aligned)
@@ -239,10 +241,10 @@ struct pb_vargs
     uint8_t *codes;          // CODES variants: one code byte per frame of the range
 };
 
-// ---- verification as sent (pbgpu_verify_wire: pb_wire_kernel, pb_wfold_kernel) ----
+// ---- verification as sent (pbgpu_verify_wire: pb_wire_kernel, pb_vfold_kernel) ----
 // pb_vst_kernel's workgroup, stage and window sizes; a record per workgroup:
-// {bad, malformed, l3 csum, l3 len | l4 csum, udp len, ipv4, ipv6 | inner, nol4, other, 0 | first bad lo, hi, 0, 0}
-#define PB_WREC_DW 16
+// bad, malformed, l3 csum, l3 len, l4 csum, udp len, ipv4, ipv6, inner, nol4, other
+#define PB_WREC_DW PB_REC_DW(11)
 struct pb_wargs
 {
     const uint8_t *data;     // frames->data (16-B aligned)

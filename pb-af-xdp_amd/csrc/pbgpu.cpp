@@ -47,9 +47,9 @@ extern "C" hipError_t pbk_launch_scatter(const uint8_t *src, const uint64_t *off
 extern "C" hipError_t pbk_launch_fill(void *dst, uint64_t bytes, int mode, hipStream_t st);
 extern "C" const char *pbk_fill_shape_name(int mode);
 extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t grid, hipStream_t st);
-extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
+extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, uint32_t ncnt, unsigned long long *out,
+                                       hipStream_t st);
 extern "C" hipError_t pbk_launch_wire(const pb_wargs *A, int G, uint32_t grid, hipStream_t st);
-extern "C" hipError_t pbk_launch_wfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_read(const void *src, uint64_t bytes, uint32_t *out, hipStream_t st);
 extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStream_t st);
 extern "C" hipError_t pbk_launch_encap(const pb_enargs *A, uint32_t grid, hipStream_t st);
@@ -251,12 +251,12 @@ struct pbgpu_ctx
     // memory (h_ctr_sum; d_ctr_sum its device address)
     unsigned long long *h_ctr_sum = nullptr, *d_ctr_sum = nullptr;
     unsigned long long *d_img_ctr = nullptr; // counters of the load-time pb_ximg_kernel page builds (never read)
-    // pbgpu_verify: the workgroups' records, the folded result in mapped pinned host memory (written
-    // by pb_vfold_kernel, as h_ctr_sum is by pb_ctr_read) and the code bytes; each grown on demand
+    // pbgpu_verify and pbgpu_verify_wire (run_check): the workgroups' records, the folded result in
+    // mapped pinned host memory (written by pb_vfold_kernel, as h_ctr_sum is by pb_ctr_read) and the
+    // code bytes; records and codes grown on demand
     uint32_t *d_vfy_rec = nullptr;
-    uint64_t vfy_rec_cap = 0; // records
-    unsigned long long *h_vres = nullptr, *d_vres = nullptr;
-    unsigned long long *h_wres = nullptr, *d_wres = nullptr; // pbgpu_verify_wire's folded result, as h_vres
+    uint64_t vfy_rec_cap = 0; // bytes
+    unsigned long long *h_vres = nullptr, *d_vres = nullptr; // PB_CHECK_RES words
     uint8_t *d_vcodes = nullptr;
     uint64_t vcodes_cap = 0;
     // pbgpu_fragment and pbgpu_segment: the count pass's scratch (result words, one or two row
@@ -648,8 +648,6 @@ void pbgpu_close(pbgpu_ctx *ctx)
         (void)hipFree(ctx->d_vfy_rec);
     if (ctx->h_vres)
         (void)hipHostFree(ctx->h_vres);
-    if (ctx->h_wres)
-        (void)hipHostFree(ctx->h_wres);
     if (ctx->d_vcodes)
         (void)hipFree(ctx->d_vcodes);
     if (ctx->d_cut_cnt)
@@ -1767,6 +1765,61 @@ static int verify_shape(const pbgpu_frames *f, uint64_t first, uint64_t n, uint6
     return vst_shape(f, n, mean, &A->wgf, &A->bf, grid);
 }
 
+// One check of frames [first, first + n), for pbgpu_verify and pbgpu_verify_wire.  A is the kernel's
+// argument block, its fields from `checks` on filled by the caller; shape(mean, &grid) chooses the
+// launch by the mean length and returns what launch(shape, grid) wants.  After it ctx->h_vres holds
+// the ncnt counts in the record's order, then the first bad index.
+#define PB_CHECK_RES 12 // the most: pbgpu_verify_wire's eleven counts and the index
+extern "C++" template <class ARGS, class SHAPE, class LAUNCH>
+static int run_check(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first, uint64_t n, ARGS &A, uint32_t ncnt,
+                     SHAPE shape, LAUNCH launch, uint8_t *codes_out, double *device_ms)
+{
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    uint64_t mean = f->fixed_len;
+    if (!f->fixed_len)
+    {
+        const int mrc = materialize_offsets(ctx, f);
+        if (mrc != PBGPU_OK)
+            return mrc;
+        uint64_t total = 0;
+        const int trc = pbgpu_frames_total(ctx, f, &total);
+        if (trc != PBGPU_OK)
+            return trc;
+        mean = total / f->n_frames;
+    }
+    A.data = f->data;
+    A.offsets = f->fixed_len ? nullptr : f->offsets;
+    A.first = first;
+    A.n = n;
+    A.fixed_len = f->fixed_len;
+    uint32_t grid = 0;
+    const int sh = shape(mean, &grid);
+    const size_t rec_bytes = (size_t)grid * PB_REC_DW(ncnt) * sizeof(uint32_t);
+    PBCHK(scratch_reserve((void **)&ctx->d_vfy_rec, &ctx->vfy_rec_cap, rec_bytes, rec_bytes));
+    if (ctx->h_vres == nullptr)
+    {
+        HIPCHK(hipHostMalloc((void **)&ctx->h_vres, PB_CHECK_RES * sizeof(unsigned long long),
+                             hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_vres, ctx->h_vres, 0));
+    }
+    if (codes_out)
+        PBCHK(scratch_reserve((void **)&ctx->d_vcodes, &ctx->vcodes_cap, n, n));
+    A.rec = ctx->d_vfy_rec;
+    A.codes = codes_out ? ctx->d_vcodes : nullptr;
+    timing_pair tp;
+    PBCHK(timed_begin(ctx, &tp));
+    HIPCHK(launch(sh, grid));
+    HIPCHK(pbk_launch_vfold(ctx->d_vfy_rec, grid, ncnt, ctx->d_vres, ctx->stream));
+    PBCHK(timed_stop(ctx, tp));
+    if (codes_out) // after the timed stretch
+        HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
+    float ms = 0;
+    PBCHK(timed_ms(ctx, tp, &ms));
+    *device_ms = ms;
+    return PBGPU_OK;
+}
+
 int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t n, uint32_t checks,
                  pbgpu_verify_result *res, uint8_t *codes_out)
 {
@@ -1785,58 +1838,21 @@ int pbgpu_verify(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uint64_t
             memset(codes_out, PBGPU_VERIFY_SHORT, n);
         return PBGPU_OK;
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    uint64_t mean = f->fixed_len;
-    if (!f->fixed_len)
-    {
-        const int mrc = materialize_offsets(ctx, f);
-        if (mrc != PBGPU_OK)
-            return mrc;
-        uint64_t total = 0;
-        const int trc = pbgpu_frames_total(ctx, f, &total);
-        if (trc != PBGPU_OK)
-            return trc;
-        mean = total / f->n_frames;
-    }
     pb_vargs A;
     memset(&A, 0, sizeof A);
-    A.data = f->data;
-    A.offsets = f->fixed_len ? nullptr : f->offsets;
-    A.first = first_frame;
-    A.n = n;
-    A.fixed_len = f->fixed_len;
     A.checks = checks & PBGPU_VERIFY_ALL;
-    uint32_t grid = 0;
-    const int shape = verify_shape(f, first_frame, n, mean, &A, &grid);
-    PBCHK(scratch_reserve((void **)&ctx->d_vfy_rec, &ctx->vfy_rec_cap, grid,
-                          (size_t)grid * PB_VREC_DW * sizeof(uint32_t)));
-    if (ctx->h_vres == nullptr)
-    {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_vres, 8 * sizeof(unsigned long long),
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_vres, ctx->h_vres, 0));
-    }
-    if (codes_out)
-        PBCHK(scratch_reserve((void **)&ctx->d_vcodes, &ctx->vcodes_cap, n, n));
-    A.rec = ctx->d_vfy_rec;
-    A.codes = codes_out ? ctx->d_vcodes : nullptr;
-    timing_pair tp;
-    PBCHK(timed_begin(ctx, &tp));
-    HIPCHK(pbk_launch_verify(&A, shape, grid, ctx->stream));
-    HIPCHK(pbk_launch_vfold(ctx->d_vfy_rec, grid, ctx->d_vres, ctx->stream));
-    PBCHK(timed_stop(ctx, tp));
-    if (codes_out) // after the timed stretch
-        HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
-    float ms = 0;
-    PBCHK(timed_ms(ctx, tp, &ms));
-    res->n_bad = ctx->h_vres[0];
-    res->bad_short = ctx->h_vres[1];
-    res->bad_ip_csum = ctx->h_vres[2];
-    res->bad_tot_len = ctx->h_vres[3];
-    res->bad_l4_csum = ctx->h_vres[4];
-    res->first_bad = ctx->h_vres[5];
-    res->device_ms = ms;
+    PBCHK(run_check(
+        ctx, f, first_frame, n, A, 5,
+        [&](uint64_t mean, uint32_t *grid) { return verify_shape(f, first_frame, n, mean, &A, grid); },
+        [&](int shape, uint32_t grid) { return pbk_launch_verify(&A, shape, grid, ctx->stream); }, codes_out,
+        &res->device_ms));
+    const unsigned long long *h = ctx->h_vres;
+    res->n_bad = h[0];
+    res->bad_short = h[1];
+    res->bad_ip_csum = h[2];
+    res->bad_tot_len = h[3];
+    res->bad_l4_csum = h[4];
+    res->first_bad = h[5];
     return PBGPU_OK;
 }
 
@@ -1862,66 +1878,27 @@ int pbgpu_verify_wire(pbgpu_ctx *ctx, pbgpu_frames *f, uint64_t first_frame, uin
             memset(codes_out, PBGPU_WIRE_MALFORMED, n);
         return PBGPU_OK;
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    uint64_t mean = f->fixed_len;
-    if (!f->fixed_len)
-    {
-        const int mrc = materialize_offsets(ctx, f);
-        if (mrc != PBGPU_OK)
-            return mrc;
-        uint64_t total = 0;
-        const int trc = pbgpu_frames_total(ctx, f, &total);
-        if (trc != PBGPU_OK)
-            return trc;
-        mean = total / f->n_frames;
-    }
     pb_wargs A;
     memset(&A, 0, sizeof A);
-    A.data = f->data;
-    A.offsets = f->fixed_len ? nullptr : f->offsets;
-    A.first = first_frame;
-    A.n = n;
-    A.fixed_len = f->fixed_len;
     A.checks = opts->checks;
     A.port = opts->vxlan_port;
-    uint32_t grid = 0;
-    const int G = vst_shape(f, n, mean, &A.wgf, &A.bf, &grid);
-    // pbgpu_verify's record buffer, counted in its records: one of this kernel's is two of them
-    PBCHK(scratch_reserve((void **)&ctx->d_vfy_rec, &ctx->vfy_rec_cap, (uint64_t)grid * 2,
-                          (size_t)grid * PB_WREC_DW * sizeof(uint32_t)));
-    if (ctx->h_wres == nullptr)
-    {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_wres, 12 * sizeof(unsigned long long),
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_wres, ctx->h_wres, 0));
-    }
-    if (codes_out)
-        PBCHK(scratch_reserve((void **)&ctx->d_vcodes, &ctx->vcodes_cap, n, n));
-    A.rec = ctx->d_vfy_rec;
-    A.codes = codes_out ? ctx->d_vcodes : nullptr;
-    timing_pair tp;
-    PBCHK(timed_begin(ctx, &tp));
-    HIPCHK(pbk_launch_wire(&A, G, grid, ctx->stream));
-    HIPCHK(pbk_launch_wfold(ctx->d_vfy_rec, grid, ctx->d_wres, ctx->stream));
-    PBCHK(timed_stop(ctx, tp));
-    if (codes_out) // after the timed stretch
-        HIPCHK(hipMemcpyAsync(codes_out, ctx->d_vcodes, n, hipMemcpyDeviceToHost, ctx->stream));
-    float ms = 0;
-    PBCHK(timed_ms(ctx, tp, &ms));
-    res->n_bad = ctx->h_wres[0];
-    res->bad_malformed = ctx->h_wres[1];
-    res->bad_l3_csum = ctx->h_wres[2];
-    res->bad_l3_len = ctx->h_wres[3];
-    res->bad_l4_csum = ctx->h_wres[4];
-    res->bad_udp_len = ctx->h_wres[5];
-    res->n_ipv4 = ctx->h_wres[6];
-    res->n_ipv6 = ctx->h_wres[7];
-    res->n_inner = ctx->h_wres[8];
-    res->n_nol4 = ctx->h_wres[9];
-    res->n_other = ctx->h_wres[10];
-    res->first_bad = ctx->h_wres[11];
-    res->device_ms = ms;
+    PBCHK(run_check(
+        ctx, f, first_frame, n, A, 11,
+        [&](uint64_t mean, uint32_t *grid) { return vst_shape(f, n, mean, &A.wgf, &A.bf, grid); },
+        [&](int G, uint32_t grid) { return pbk_launch_wire(&A, G, grid, ctx->stream); }, codes_out, &res->device_ms));
+    const unsigned long long *h = ctx->h_vres;
+    res->n_bad = h[0];
+    res->bad_malformed = h[1];
+    res->bad_l3_csum = h[2];
+    res->bad_l3_len = h[3];
+    res->bad_l4_csum = h[4];
+    res->bad_udp_len = h[5];
+    res->n_ipv4 = h[6];
+    res->n_ipv6 = h[7];
+    res->n_inner = h[8];
+    res->n_nol4 = h[9];
+    res->n_other = h[10];
+    res->first_bad = h[11];
     return PBGPU_OK;
 }
 
@@ -2015,6 +1992,81 @@ int pbgpu_read_probe_at(pbgpu_ctx *ctx, const void *src, uint64_t bytes, uint32_
     return PBGPU_OK;
 }
 
+// ---- the insert writers: pcap pack, encap, xlat46 ----
+// Their output record is a source frame plus `add` bytes; they share their start and end, as the
+// cut calls share cut_run.
+
+static bool ins_pair_ok(const pbgpu_frames *src, const pbgpu_frames *dst)
+{
+    return src != dst && src->data != NULL && dst->data != NULL && !buffers_overlap(src, dst);
+}
+
+// What the shared body leaves for the call's launch and result
+struct ins_state
+{
+    uint64_t total, end16; // output bytes, and rounded up to 16: what is written
+    uint32_t per, grid;    // the writer's launch over the output's 4-KiB pages
+    hipStream_t st;
+    timing_pair tp;
+    float ms;
+};
+
+// the arguments every writer's block has
+extern "C++" template <class ARGS>
+static void ins_args(ARGS *A, const pbgpu_frames *src, const pbgpu_frames *dst, uint64_t first, uint64_t n,
+                     uint32_t add)
+{
+    memset(A, 0, sizeof *A);
+    A->src = src->data;
+    A->offsets = src->fixed_len ? nullptr : src->offsets;
+    A->dst = dst->data;
+    A->first = first;
+    A->n = n;
+    A->fixed_len = src->fixed_len;
+    A->rec = make_div(src->fixed_len + add);
+}
+
+// The call after its own argument checks and range_bytes: `head` bytes (pcap's file header), then n
+// records of a frame plus `add` bytes.  frames: dst holds frames afterwards (else a byte stream: no
+// frame count, no lengths, no built event).  classify(r) runs once dst is known to be large enough
+// and before anything of it is touched; it may refuse the call, and may begin the timed stretch
+// (r.tp) itself.  launch(r) queues the writer.
+extern "C++" template <class CLASSIFY, class LAUNCH>
+static int ins_run(pbgpu_ctx *ctx, const pbgpu_frames *src, uint64_t n, pbgpu_frames *dst, uint64_t body,
+                   uint64_t src_end, uint32_t head, uint32_t add, bool frames, CLASSIFY classify, LAUNCH launch,
+                   ins_state *r)
+{
+    if (src_end > src->capacity_bytes)
+        return PBGPU_EINVAL;
+    r->total = head + (uint64_t)add * n + body;
+    r->end16 = (r->total + 15) & ~15ull;
+    if ((frames && n > dst->capacity_frames) || r->end16 > dst->capacity_bytes)
+        return PBGPU_ENOSPC;
+    HIPCHK(hipSetDevice(ctx->device));
+    PB_JOIN(ctx);
+    r->st = ctx->stream;
+    r->tp = {nullptr, nullptr};
+    r->ms = 0;
+    PBCHK(classify(*r));
+    const frames_events *fs = (const frames_events *)src->reserved;
+    const bool lens = frames && n; // a byte stream has no frames, so no lengths
+    PBCHK(take_dst(dst, r->st, lens ? fs->min_len + add : 0, lens ? fs->max_len + add : 0, nullptr));
+    if (r->end16)
+    {
+        PBCHK(page_grid((r->end16 + 4095) >> 12, ctx->opt.rp_per, &r->per, &r->grid));
+        if (r->tp.a == nullptr)
+            PBCHK(timed_begin(ctx, &r->tp));
+        HIPCHK(launch(*r));
+        PBCHK(timed_stop(ctx, r->tp));
+        PBCHK(timed_ms(ctx, r->tp, &r->ms));
+    }
+    dst->first_iter = 0;
+    dst->n_frames = frames ? n : 0;
+    dst->fixed_len = frames && src->fixed_len ? src->fixed_len + add : 0;
+    dst->total_bytes = r->total;
+    return frames ? mark_built(ctx, dst, r->st) : PBGPU_OK;
+}
+
 // ---- pcap stream packing ----
 
 #define PB_PCAP_FLAGS (PBGPU_PCAP_FILE_HEADER | PBGPU_PCAP_NSEC)
@@ -2035,7 +2087,7 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL || nbytes == NULL || opts->reserved != 0)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+    if (!ins_pair_ok(src, dst))
         return PBGPU_EINVAL;
     if (opts->flags & ~PB_PCAP_FLAGS)
         return PBGPU_EINVAL;
@@ -2043,50 +2095,25 @@ int pbgpu_pcap_pack(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uin
         return PBGPU_EINVAL;
     uint64_t body = 0, src_end = 0;
     PBCHK(range_bytes(ctx, src, first_frame, n, &body, &src_end));
-    if (src_end > src->capacity_bytes)
-        return PBGPU_EINVAL;
-    const uint32_t H = (opts->flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u;
-    const uint64_t total = H + 16u * n + body;
-    const uint64_t end16 = (total + 15) & ~15ull;
-    if (end16 > dst->capacity_bytes)
-        return PBGPU_ENOSPC;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    hipStream_t st = ctx->stream;
-    PBCHK(take_dst(dst, st, 0, 0, nullptr)); // a byte stream: no frames, so no lengths
-    dst->first_iter = 0;
-    dst->n_frames = 0;
-    dst->fixed_len = 0;
-    dst->total_bytes = total;
-    float ms = 0;
-    if (end16)
-    {
-        pb_pcargs A;
-        memset(&A, 0, sizeof A);
-        A.src = src->data;
-        A.offsets = src->fixed_len ? nullptr : src->offsets;
-        A.dst = dst->data;
-        A.first = first_frame;
-        A.n = n;
-        A.fixed_len = src->fixed_len;
-        A.rec = make_div(src->fixed_len + 16u);
-        A.flags = opts->flags;
-        A.hdr = H;
-        A.end16 = end16;
-        A.t0_ns = opts->t0_ns;
-        A.step_ps = opts->step_ps;
-        A.first_index = opts->first_index;
-        uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
-        timing_pair tp;
-        PBCHK(timed_begin(ctx, &tp));
-        HIPCHK(pbk_launch_pcap(&A, grid, st));
-        PBCHK(timed_stop(ctx, tp));
-        PBCHK(timed_ms(ctx, tp, &ms));
-    }
-    *nbytes = total;
+    pb_pcargs A;
+    ins_args(&A, src, dst, first_frame, n, 16u);
+    A.flags = opts->flags;
+    A.hdr = (opts->flags & PBGPU_PCAP_FILE_HEADER) ? 24u : 0u;
+    A.t0_ns = opts->t0_ns;
+    A.step_ps = opts->step_ps;
+    A.first_index = opts->first_index;
+    ins_state r;
+    PBCHK(ins_run(
+        ctx, src, n, dst, body, src_end, A.hdr, 16u, false, [](ins_state &) { return PBGPU_OK; },
+        [&](ins_state &r) {
+            A.end16 = r.end16;
+            A.per = r.per;
+            return pbk_launch_pcap(&A, r.grid, r.st);
+        },
+        &r));
+    *nbytes = r.total;
     if (device_ms)
-        *device_ms = ms;
+        *device_ms = r.ms;
     return PBGPU_OK;
 }
 
@@ -2128,39 +2155,17 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+    if (!ins_pair_ok(src, dst))
         return PBGPU_EINVAL;
     uint32_t P = 0;
     uint64_t body = 0, src_end = 0;
     PBCHK(encap_check(ctx, src, first_frame, n, opts, &P, &body, &src_end));
-    if (src_end > src->capacity_bytes)
-        return PBGPU_EINVAL;
-    const uint64_t total = body + n * P;
-    const uint64_t end16 = (total + 15) & ~15ull;
-    if (n > dst->capacity_frames || end16 > dst->capacity_bytes)
-        return PBGPU_ENOSPC;
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    const frames_events *fs = (const frames_events *)src->reserved;
-    const uint32_t src_min = fs->min_len, src_max = fs->max_len;
-    hipStream_t st = ctx->stream;
-    PBCHK(take_dst(dst, st, n ? src_min + P : 0, n ? src_max + P : 0, nullptr));
-    float ms = 0;
-    if (n)
+    pb_enargs A;
+    ins_args(&A, src, dst, first_frame, n, P);
+    A.dst_offsets = dst->offsets;
+    A.P = P;
+    A.hdw = (P + 6u) / 4u; // P + 3 bytes in dwords
     {
-        pb_enargs A;
-        memset(&A, 0, sizeof A);
-        A.src = src->data;
-        A.offsets = src->fixed_len ? nullptr : src->offsets;
-        A.dst = dst->data;
-        A.dst_offsets = dst->offsets;
-        A.first = first_frame;
-        A.n = n;
-        A.end16 = end16;
-        A.fixed_len = src->fixed_len;
-        A.rec = make_div(src->fixed_len + P);
-        A.P = P;
-        A.hdw = (P + 6u) / 4u; // P + 3 bytes in dwords
         uint8_t t[PB_EN_TDW * 4];
         memset(t, 0, sizeof t);
         if (opts->mode == PBGPU_ENCAP_VLAN)
@@ -2202,21 +2207,19 @@ int pbgpu_encap(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64_
             }
         }
         pack_le32(A.tpl, t, PB_EN_TDW);
-        uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
-        timing_pair tp;
-        PBCHK(timed_begin(ctx, &tp));
-        HIPCHK(pbk_launch_encap(&A, grid, st)); // variable length: dst->offsets by a launch of its own first
-        PBCHK(timed_stop(ctx, tp));
-        PBCHK(timed_ms(ctx, tp, &ms));
     }
-    dst->first_iter = 0;
-    dst->n_frames = n;
-    dst->fixed_len = src->fixed_len ? src->fixed_len + P : 0;
-    dst->total_bytes = total;
+    ins_state r;
+    PBCHK(ins_run(
+        ctx, src, n, dst, body, src_end, 0u, P, true, [](ins_state &) { return PBGPU_OK; },
+        [&](ins_state &r) {
+            A.end16 = r.end16;
+            A.per = r.per;
+            return pbk_launch_encap(&A, r.grid, r.st); // variable length: dst->offsets by a launch of its own first
+        },
+        &r));
     if (device_ms)
-        *device_ms = ms;
-    return mark_built(ctx, dst, st);
+        *device_ms = r.ms;
+    return PBGPU_OK;
 }
 
 // ---- cutting frames into pieces: IPv4 fragmentation and L4 segmentation ----
@@ -2650,100 +2653,77 @@ int pbgpu_xlat46(pbgpu_ctx *ctx, pbgpu_frames *src, uint64_t first_frame, uint64
 {
     if (ctx == NULL || src == NULL || opts == NULL || dst == NULL)
         return PBGPU_EINVAL;
-    if (src == dst || src->data == NULL || dst->data == NULL || buffers_overlap(src, dst))
+    if (!ins_pair_ok(src, dst))
         return PBGPU_EINVAL;
     uint64_t body = 0, src_end = 0;
     PBCHK(xlat_check(ctx, src, first_frame, n, opts, &body, &src_end));
-    if (src_end > src->capacity_bytes)
-        return PBGPU_EINVAL;
-    const uint64_t total = body + n * PB_XL_ADD;
-    const uint64_t end16 = (total + 15) & ~15ull;
-    if (n > dst->capacity_frames || end16 > dst->capacity_bytes)
-        return PBGPU_ENOSPC;
-    if (n > (uint64_t)0xFFFFFFFFu * (PB_XL_WT * PB_XL_ROWS))
-        return PBGPU_EINVAL;
-    if (res)
-    {
-        memset(res, 0, sizeof *res);
-        res->n_in = n;
-        res->first_other = UINT64_MAX;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    PB_JOIN(ctx);
-    const frames_events *fs = (const frames_events *)src->reserved;
-    const uint32_t src_min = fs->min_len, src_max = fs->max_len;
-    hipStream_t st = ctx->stream;
     pb_xlargs A;
-    memset(&A, 0, sizeof A);
-    timing_pair tp = {nullptr, nullptr};
-    float ms = 0;
-    if (n)
-    {
+    ins_args(&A, src, dst, first_frame, n, PB_XL_ADD);
+    A.dst_offsets = dst->offsets;
+    A.flags = (opts->flags & PBGPU_XLAT_HASH_FLOW) ? PB_XL_HASH : 0u;
+    A.flow_label = opts->flow_label;
+    uint8_t t[32]; // output bytes 20..51
+    memset(t, 0, sizeof t);
+    memcpy(t + 2, opts->src_prefix, 12);
+    memcpy(t + 18, opts->dst_prefix, 12);
+    for (int i = 0; i < 32; i += 2)
+        A.ksum += ((uint32_t)t[i] << 8) | t[i + 1];
+    while (A.ksum >> 16)
+        A.ksum = (A.ksum & 0xFFFFu) + (A.ksum >> 16);
+    pack_le32(A.tpl, t, 8);
+    // The classify stage: its result is read before anything of dst is touched, and a frame that does
+    // not translate refuses the call.  The timed stretch is classify and writer.
+    auto classify = [&](ins_state &r) -> int {
+        if (n > (uint64_t)0xFFFFFFFFu * (PB_XL_WT * PB_XL_ROWS))
+            return PBGPU_EINVAL;
+        if (res)
+        {
+            memset(res, 0, sizeof *res);
+            res->n_in = n;
+            res->first_other = UINT64_MAX;
+        }
+        if (n == 0)
+            return PBGPU_OK;
         if (ctx->d_xl_res == nullptr)
             HIPCHK(hipMalloc((void **)&ctx->d_xl_res, PB_XL_RES_DW * sizeof(unsigned long long)));
-        A.src = src->data;
-        A.offsets = src->fixed_len ? nullptr : src->offsets;
-        A.first = first_frame;
-        A.n = n;
-        A.end16 = end16;
-        A.fixed_len = src->fixed_len;
-        A.rec = make_div(src->fixed_len + PB_XL_ADD);
-        A.flags = (opts->flags & PBGPU_XLAT_HASH_FLOW) ? PB_XL_HASH : 0u;
-        A.flow_label = opts->flow_label;
         A.res = ctx->d_xl_res;
-        uint8_t t[32]; // output bytes 20..51
-        memset(t, 0, sizeof t);
-        memcpy(t + 2, opts->src_prefix, 12);
-        memcpy(t + 18, opts->dst_prefix, 12);
-        for (int i = 0; i < 32; i += 2)
-            A.ksum += ((uint32_t)t[i] << 8) | t[i + 1];
-        while (A.ksum >> 16)
-            A.ksum = (A.ksum & 0xFFFFu) + (A.ksum >> 16);
-        pack_le32(A.tpl, t, 8);
-        // the timed stretch: classify and writer; the classify result is read before anything of dst is touched
-        PBCHK(timed_begin(ctx, &tp));
-        HIPCHK(pbk_launch_xlat(&A, 0, 0, st));
-        unsigned long long r[PB_XL_RES_DW];
-        HIPCHK(hipMemcpyAsync(r, ctx->d_xl_res, sizeof r, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (r[0] + r[1] + r[2] + r[3] != n)
+        A.end16 = r.end16;
+        PBCHK(timed_begin(ctx, &r.tp));
+        HIPCHK(pbk_launch_xlat(&A, 0, 0, r.st));
+        unsigned long long c[PB_XL_RES_DW];
+        HIPCHK(hipMemcpyAsync(c, ctx->d_xl_res, sizeof c, hipMemcpyDeviceToHost, r.st));
+        HIPCHK(hipStreamSynchronize(r.st));
+        if (c[0] + c[1] + c[2] + c[3] != n)
             return PBGPU_EIO;
         if (res)
         {
-            res->n_udp = r[0];
-            res->n_tcp = r[1];
-            res->n_icmp = r[2];
-            res->n_other = r[3];
-            res->first_other = r[4];
+            res->n_udp = c[0];
+            res->n_tcp = c[1];
+            res->n_icmp = c[2];
+            res->n_other = c[3];
+            res->first_other = c[4];
         }
-        if (r[3])
+        if (c[3])
         {
-            PBCHK(timed_stop(ctx, tp));
-            PBCHK(timed_ms(ctx, tp, &ms));
+            PBCHK(timed_stop(ctx, r.tp));
+            PBCHK(timed_ms(ctx, r.tp, &r.ms));
             if (res)
-                res->device_ms = ms;
+                res->device_ms = r.ms;
             return PBGPU_EINVAL;
         }
-    }
-    // every frame of the range is translatable: at least 42 B
-    PBCHK(take_dst(dst, st, n ? src_min + PB_XL_ADD : 0, n ? src_max + PB_XL_ADD : 0, nullptr));
-    if (n)
-    {
-        A.dst = dst->data;
-        A.dst_offsets = dst->offsets;
-        uint32_t grid = 0;
-        PBCHK(page_grid((end16 + 4095) >> 12, ctx->opt.rp_per, &A.per, &grid));
-        HIPCHK(pbk_launch_xlat(&A, 1, grid, st)); // variable length: dst->offsets by a launch of its own first
-        PBCHK(timed_stop(ctx, tp));
-        PBCHK(timed_ms(ctx, tp, &ms));
-    }
-    dst->first_iter = 0;
-    dst->n_frames = n;
-    dst->fixed_len = src->fixed_len ? src->fixed_len + PB_XL_ADD : 0;
-    dst->total_bytes = total;
+        return PBGPU_OK; // every frame of the range is translatable: at least 42 B
+    };
+    ins_state r;
+    PBCHK(ins_run(
+        ctx, src, n, dst, body, src_end, 0u, PB_XL_ADD, true, classify,
+        [&](ins_state &r) {
+            A.per = r.per;
+            return pbk_launch_xlat(&A, 1, r.grid, r.st); // variable length: dst->offsets by a launch of its own first
+        },
+        &r));
     if (res)
-        res->device_ms = ms;
-    return mark_built(ctx, dst, st);
+        res->device_ms = r.ms;
+    return PBGPU_OK;
 }
 
 int pbgpu_host_register(pbgpu_ctx *ctx, void *ptr, size_t bytes)

@@ -3794,22 +3794,51 @@ __device__ __forceinline__ uint32_t pb_vcode(uint32_t ip, uint32_t ps, uint32_t 
     return code & checks;
 }
 
+// ---- the scaffold of the two verifiers (pbgpu_verify, pbgpu_verify_wire: DESIGN.md 5.8, 5.14) ----
+// Tally, record, epilogue and fold, and for the staged kernels (pb_vst_kernel, pb_wire_kernel) the
+// window reader, the head fetch and the masked chunk sum, exist once.  A kind (pb_v_kind here,
+// pb_w_kind with the wire verifier) supplies
+//   N, mask()   its counters, as the code bits each one counts; mask(0) is "bad", whose first
+//               index is kept
+//   NF, SKIP    the first NF counters count failures; SKIP: a wave whose frames are all clean
+//               passes them by (wave-uniform)
+// and the kernels give the head fetch its slot size and the chunk sum its second range at compile
+// time.
+
 // a wave's tallies (the counts are wave-uniform, first is per lane)
-struct pb_vcount
+template <int N>
+struct pb_tally
 {
-    uint32_t bad, sh, ip, tl, l4;
+    uint32_t c[N];
     uint64_t first;
 };
 
-__device__ __forceinline__ void pb_vtally(pb_vcount &c, bool lead, uint32_t code, uint64_t f)
+struct pb_v_kind
 {
-    c.bad += (uint32_t)__popcll(__ballot(lead && code != 0));
-    c.sh += (uint32_t)__popcll(__ballot(lead && (code & 8u)));
-    c.ip += (uint32_t)__popcll(__ballot(lead && (code & 1u)));
-    c.tl += (uint32_t)__popcll(__ballot(lead && (code & 2u)));
-    c.l4 += (uint32_t)__popcll(__ballot(lead && (code & 4u)));
-    if (lead && code != 0 && f < c.first)
-        c.first = f;
+    static constexpr int N = 5, NF = 5; // bad, short, ip, tot_len, l4
+    static constexpr bool SKIP = false;
+    static __device__ __forceinline__ constexpr uint32_t mask(int k)
+    {
+        constexpr uint32_t m[N] = {~0u, 8u, 1u, 2u, 4u}; // bad: any bit of the code
+        return m[k];
+    }
+};
+
+template <class KIND>
+__device__ __forceinline__ void pb_tally_add(pb_tally<KIND::N> &c, bool lead, uint32_t code, uint64_t f)
+{
+    const bool bad = lead && (code & KIND::mask(0));
+    if (!KIND::SKIP || __ballot(bad)) // wave-uniform: clean frames skip the failure counts
+    {
+#pragma unroll
+        for (int k = 0; k < KIND::NF; ++k)
+            c.c[k] += (uint32_t)__popcll(__ballot(lead && (code & KIND::mask(k))));
+        if (bad && f < c.first)
+            c.first = f;
+    }
+#pragma unroll
+    for (int k = KIND::NF; k < KIND::N; ++k)
+        c.c[k] += (uint32_t)__popcll(__ballot(lead && (code & KIND::mask(k))));
 }
 
 __device__ __forceinline__ uint64_t pb_vwave_min(uint64_t v)
@@ -3823,13 +3852,64 @@ __device__ __forceinline__ uint64_t pb_vwave_min(uint64_t v)
     return v;
 }
 
-// a workgroup's record: two plain 16-B stores
-__device__ __forceinline__ void pb_vrecord(uint32_t *rec, uint32_t wg, uint32_t bad, uint32_t sh, uint32_t ip,
-                                           uint32_t tl, uint32_t l4, uint64_t first)
+// a workgroup's record (PB_REC_DW(N) dwords: the N counts, the first bad index, zeros): plain 16-B stores
+template <int N>
+__device__ __forceinline__ void pb_tally_record(uint32_t *rec, uint32_t wg, const uint32_t (&t)[N], uint64_t first)
 {
-    pb_u32x4 *r = reinterpret_cast<pb_u32x4 *>(rec + (size_t)wg * PB_VREC_DW);
-    r[0] = pb_u32x4{bad, sh, ip, tl};
-    r[1] = pb_u32x4{l4, 0u, (uint32_t)first, (uint32_t)(first >> 32)};
+    uint32_t d[PB_REC_DW(N)] = {};
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        d[k] = t[k];
+    d[N] = (uint32_t)first, d[N + 1] = (uint32_t)(first >> 32);
+    pb_u32x4 *r = reinterpret_cast<pb_u32x4 *>(rec + (size_t)wg * PB_REC_DW(N));
+#pragma unroll
+    for (int k = 0; k < PB_REC_DW(N) / 4; ++k)
+        r[k] = pb_u32x4{d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
+}
+
+// The epilogue: the waves' tallies (wave min of first, a row of s_cnt per wave) folded by thread 0
+// into the workgroup's record.  One wave (pb_vpg_kernel) needs no LDS row and passes none.
+template <int N, uint32_t NWV>
+__device__ __forceinline__ void pb_tally_finish(const pb_tally<N> &c, uint32_t *rec,
+                                                uint32_t (*s_cnt)[PB_REC_DW(N)] = nullptr)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint64_t first = pb_vwave_min(c.first);
+    if constexpr (NWV == 1)
+    {
+        if (tid == 0)
+            pb_tally_record<N>(rec, blockIdx.x, c.c, first);
+    }
+    else
+    {
+        if ((tid & 63u) == 0)
+        {
+            uint32_t *r = s_cnt[tid >> 6];
+#pragma unroll
+            for (int k = 0; k < N; ++k)
+                r[k] = c.c[k];
+            r[N] = (uint32_t)first, r[N + 1] = (uint32_t)(first >> 32);
+        }
+        __syncthreads();
+        if (tid == 0)
+        {
+            uint32_t t[N];
+            uint64_t mn = ~0ull;
+#pragma unroll
+            for (int k = 0; k < N; ++k)
+            {
+                t[k] = 0;
+                for (uint32_t w = 0; w < NWV; ++w)
+                    t[k] += s_cnt[w][k];
+            }
+            for (uint32_t w = 0; w < NWV; ++w)
+            {
+                const uint64_t m = s_cnt[w][N] | (uint64_t)s_cnt[w][N + 1] << 32;
+                mn = m < mn ? m : mn;
+            }
+            pb_tally_record<N>(rec, blockIdx.x, t, mn);
+        }
+    }
 }
 
 // Fixed length, 34 to 128 B: pb_xsmall_kernel / pb_xpage_kernel's page ownership read backwards.  A
@@ -3856,7 +3936,7 @@ __global__ __launch_bounds__(64) void pb_vpg_kernel(pb_vargs A)
     uint64_t fcur = (base + flen - 1u) / flen; // the first frame starting in the wave's pages
     if (fcur < A.first)
         fcur = A.first;
-    pb_vcount c = {0, 0, 0, 0, 0, ~0ull};
+    pb_tally<5> c = {{0, 0, 0, 0, 0}, ~0ull};
     for (uint64_t pg = pg_a; pg < pg_b; ++pg, base += PB_XPG)
     {
         const uint8_t *src = A.data + base;
@@ -3923,15 +4003,13 @@ __global__ __launch_bounds__(64) void pb_vpg_kernel(pb_vargs A)
                 seg = pb_add_halves(seg, w);
             }
             const uint32_t code = valid ? pb_vcode(ip, ps, tot_len, proto, pb_fold(seg), flen, A.checks) : 0u;
-            pb_vtally(c, valid, code, fcur + s);
+            pb_tally_add<pb_v_kind>(c, valid, code, fcur + s);
             if (CODES && valid)
                 A.codes[fcur + s - A.first] = (uint8_t)code;
         }
         fcur += cnt;
     }
-    const uint64_t first = pb_vwave_min(c.first);
-    if (lane == 0)
-        pb_vrecord(A.rec, blockIdx.x, c.bad, c.sh, c.ip, c.tl, c.l4, first);
+    pb_tally_finish<5, 1>(c, A.rec);
 }
 
 // Everything else: longer fixed frames and packed variable-length frames at any byte offset.  A
@@ -3943,61 +4021,139 @@ __global__ __launch_bounds__(64) void pb_vpg_kernel(pb_vargs A)
 // window that does not fit the stage (frames up to 65,535 B) is summed from global memory with
 // the same aligned 16-B loads, the edge chunks byte-masked (pb_bytemask); only its frames' first
 // chunks pass through LDS, for the header dwords.
+
+// a window of a workgroup's frames: wn frames from g0, their positions in s_off[0 .. wn] relative to
+// src (16-B aligned); staged: the window's span16 bytes are in the stage
+struct pb_vs_win
+{
+    uint32_t wn, span16;
+    uint64_t g0;
+    const uint8_t *src;
+    bool staged;
+};
+
+// The window reader: frames [w0, w0 + A.bf) of the workgroup's [fa, fe), from the previous window's
+// last read to the barrier after the stage load.  ARGS: pb_vargs or pb_wargs.
+template <class ARGS>
+__device__ __forceinline__ pb_vs_win pb_vs_window(const ARGS &A, uint64_t w0, uint64_t fa, uint64_t fe,
+                                                  pb_u32x4 *s_stage, uint32_t *s_off)
+{
+    const uint32_t tid = threadIdx.x;
+    pb_vs_win W;
+    W.wn = fe - w0 < A.bf ? (uint32_t)(fe - w0) : A.bf;
+    W.g0 = A.first + w0;
+    const uint64_t sb = A.offsets ? A.offsets[W.g0] : W.g0 * A.fixed_len;
+    const uint64_t eb = A.offsets ? A.offsets[W.g0 + W.wn] : (W.g0 + W.wn) * A.fixed_len;
+    const uint64_t s16 = sb & ~15ull;
+    W.staged = eb - s16 <= PB_VS_STAGE;
+    W.span16 = (uint32_t)((eb - s16 + 15ull) & ~15ull); // < 2^26: bf frames of < 64 KiB
+    W.src = A.data + s16;
+    if (w0 != fa)
+        __syncthreads(); // the previous window has been summed
+    for (uint32_t i = tid; i <= W.wn; i += PB_VST_WT)
+        s_off[i] = (uint32_t)((A.offsets ? A.offsets[W.g0 + i] : (W.g0 + i) * A.fixed_len) - s16);
+    if (W.staged)
+        for (uint32_t ch = tid; ch < (W.span16 >> 4); ch += PB_VST_WT)
+            s_stage[ch] = *reinterpret_cast<const pb_u32x4 *>(W.src + 16u * ch);
+    __syncthreads();
+    return W;
+}
+
+// The head fetch of an un-staged window: the first NCH chunks of the frame at p into the group's slot
+// of NCH x 16 B (a group is inside one wave); the frame's first byte in the stage is returned
+template <int G, uint32_t NCH>
+__device__ __forceinline__ uint32_t pb_vs_head(const pb_vs_win &W, pb_u32x4 *s_stage, uint32_t grp, uint32_t gl,
+                                               uint32_t p)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (uint32_t k0 = 0; k0 < NCH; k0 += G)
+    {
+        const uint32_t k = k0 + gl;
+        if (k < NCH)
+        {
+            const uint32_t cb = (p & ~15u) + 16u * k;
+            s_stage[grp * NCH + k] =
+                cb < W.span16 ? *reinterpret_cast<const pb_u32x4 *>(W.src + cb) : pb_u32x4{0, 0, 0, 0};
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return grp * (16u * NCH) + (p & 15u);
+}
+
+// The masked chunk sum: a group's lanes add the 16-B chunks holding bytes [lo, hi) of a frame (hi >
+// lo), from the stage or from global memory, the edge chunks byte-masked, into acc0.  TWO: a second
+// range [lo1, hi) inside the first, from chunk c0b on (~0u: none), takes the same loads into acc1.
+template <int G, bool TWO>
+__device__ __forceinline__ void pb_vs_sum(const pb_vs_win &W, const pb_u32x4 *s_stage, uint32_t gl, uint32_t lo,
+                                          uint32_t hi, uint32_t lo1, uint32_t c0b, uint32_t &acc0, uint32_t &acc1)
+{
+    const uint32_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
+    for (uint32_t ch = c0 + gl; ch <= c1; ch += G)
+    {
+        pb_u32x4 v;
+        if (W.staged)
+            v = s_stage[ch];
+        else
+            v = *reinterpret_cast<const pb_u32x4 *>(W.src + 16u * ch);
+        if (ch == c0 || ch == c1)
+        {
+            const int a = (int)lo - (int)(16u * ch), b = (int)hi - (int)(16u * ch);
+            v.x &= pb_bytemask(a, b, 0);
+            v.y &= pb_bytemask(a, b, 1);
+            v.z &= pb_bytemask(a, b, 2);
+            v.w &= pb_bytemask(a, b, 3);
+        }
+        acc0 = pb_add_halves(acc0, v.x);
+        acc0 = pb_add_halves(acc0, v.y);
+        acc0 = pb_add_halves(acc0, v.z);
+        acc0 = pb_add_halves(acc0, v.w);
+        if (TWO && ch >= c0b)
+        {
+            if (ch == c0b)
+            {
+                const int a = (int)lo1 - (int)(16u * ch);
+                v.x &= pb_bytemask(a, 16, 0);
+                v.y &= pb_bytemask(a, 16, 1);
+                v.z &= pb_bytemask(a, 16, 2);
+                v.w &= pb_bytemask(a, 16, 3);
+            }
+            acc1 = pb_add_halves(acc1, v.x);
+            acc1 = pb_add_halves(acc1, v.y);
+            acc1 = pb_add_halves(acc1, v.z);
+            acc1 = pb_add_halves(acc1, v.w);
+        }
+    }
+}
+
 template <int G, bool CODES>
 __global__ __launch_bounds__(PB_VST_WT) void pb_vst_kernel(pb_vargs A)
 {
     constexpr uint32_t NG = PB_VST_WT / G, NWV = PB_VST_WT / 64;
     __shared__ pb_u32x4 s_stage[(PB_VS_STAGE + PB_VS_SLACK) / 16];
     __shared__ uint32_t s_off[PB_VS_BF_MAX + 1];
-    __shared__ uint32_t s_cnt[NWV][8];
+    __shared__ uint32_t s_cnt[NWV][PB_VREC_DW];
     const uint32_t *dw = reinterpret_cast<const uint32_t *>(s_stage);
     const uint32_t tid = threadIdx.x, grp = tid / G, gl = tid % G;
     const uint64_t fa = (uint64_t)pb_xcd_region(blockIdx.x, gridDim.x) * A.wgf;
     const uint64_t fe = fa + A.wgf < A.n ? fa + A.wgf : A.n;
-    pb_vcount c = {0, 0, 0, 0, 0, ~0ull};
+    pb_tally<5> c = {{0, 0, 0, 0, 0}, ~0ull};
     for (uint64_t w0 = fa; w0 < fe; w0 += A.bf)
     {
-        const uint32_t wn = fe - w0 < A.bf ? (uint32_t)(fe - w0) : A.bf;
-        const uint64_t g0 = A.first + w0;
-        const uint64_t sb = A.offsets ? A.offsets[g0] : g0 * A.fixed_len;
-        const uint64_t eb = A.offsets ? A.offsets[g0 + wn] : (g0 + wn) * A.fixed_len;
-        const uint64_t s16 = sb & ~15ull;
-        const bool staged = eb - s16 <= PB_VS_STAGE;
-        const uint32_t span16 = (uint32_t)((eb - s16 + 15ull) & ~15ull); // < 2^26: bf frames of < 64 KiB
-        const uint8_t *src = A.data + s16;
-        if (w0 != fa)
-            __syncthreads(); // the previous window has been summed
-        for (uint32_t i = tid; i <= wn; i += PB_VST_WT)
-            s_off[i] = (uint32_t)((A.offsets ? A.offsets[g0 + i] : (g0 + i) * A.fixed_len) - s16);
-        if (staged)
-            for (uint32_t ch = tid; ch < (span16 >> 4); ch += PB_VST_WT)
-                s_stage[ch] = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
-        __syncthreads();
-        for (uint32_t r0 = 0; r0 < wn; r0 += NG)
+        const pb_vs_win W = pb_vs_window(A, w0, fa, fe, s_stage, s_off);
+        for (uint32_t r0 = 0; r0 < W.wn; r0 += NG)
         {
             const uint32_t fi = r0 + grp;
-            const bool valid = fi < wn;
+            const bool valid = fi < W.wn;
             const uint32_t p = s_off[valid ? fi : 0u], q = s_off[valid ? fi + 1u : 0u];
             const uint32_t len = q - p;
-            uint32_t hb = p;
-            if (!staged)
-            {
-                // the frame's first four chunks into the group's 64-B slot (a group is inside one wave)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (gl < 4u)
-                {
-                    const uint32_t cb = (p & ~15u) + 16u * gl;
-                    s_stage[grp * 4u + gl] =
-                        cb < span16 ? *reinterpret_cast<const pb_u32x4 *>(src + cb) : pb_u32x4{0, 0, 0, 0};
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                hb = grp * 64u + (p & 15u);
-            }
-            uint32_t ip = 0, ps = 0, meta = 0, acc = 0;
+            // un-staged: the frame's first four chunks, for the header dwords
+            const uint32_t hb = W.staged ? p : pb_vs_head<G, 4>(W, s_stage, grp, gl, p);
+            uint32_t ip = 0, ps = 0, meta = 0, acc = 0, none = 0;
             if (gl < 6u)
             {
                 const uint32_t w = pb_vdw(dw, hb + 12u + 4u * gl); // frame bytes 12 + 4 gl ..
@@ -4016,30 +4172,7 @@ __global__ __launch_bounds__(PB_VST_WT) void pb_vst_kernel(pb_vargs A)
                     ip = ps = w & 0xFFFFu;
             }
             if (len > 34u)
-            {
-                const uint32_t lo = p + 34u, hi = q;
-                const uint32_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
-                for (uint32_t ch = c0 + gl; ch <= c1; ch += G)
-                {
-                    pb_u32x4 v;
-                    if (staged)
-                        v = s_stage[ch];
-                    else
-                        v = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
-                    if (ch == c0 || ch == c1)
-                    {
-                        const int a = (int)lo - (int)(16u * ch), b = (int)hi - (int)(16u * ch);
-                        v.x &= pb_bytemask(a, b, 0);
-                        v.y &= pb_bytemask(a, b, 1);
-                        v.z &= pb_bytemask(a, b, 2);
-                        v.w &= pb_bytemask(a, b, 3);
-                    }
-                    acc = pb_add_halves(acc, v.x);
-                    acc = pb_add_halves(acc, v.y);
-                    acc = pb_add_halves(acc, v.z);
-                    acc = pb_add_halves(acc, v.w);
-                }
-            }
+                pb_vs_sum<G, false>(W, s_stage, gl, p + 34u, q, 0u, 0u, acc, none);
             acc = pb_group_sum<G>(acc);
             ip = pb_group_sum<G>(ip);
             ps = pb_group_sum<G>(ps);
@@ -4049,72 +4182,58 @@ __global__ __launch_bounds__(PB_VST_WT) void pb_vst_kernel(pb_vargs A)
                 seg = pb_bswap16(seg);
             const bool lead = valid && gl == 0u;
             const uint32_t code = lead ? pb_vcode(ip, ps, meta & 0xFFFFu, meta >> 16, seg, len, A.checks) : 0u;
-            pb_vtally(c, lead, code, g0 + fi);
+            pb_tally_add<pb_v_kind>(c, lead, code, W.g0 + fi);
             if (CODES && lead)
                 A.codes[w0 + fi] = (uint8_t)code;
         }
     }
-    const uint64_t first = pb_vwave_min(c.first);
-    if ((tid & 63u) == 0)
-    {
-        uint32_t *r = s_cnt[tid >> 6];
-        r[0] = c.bad, r[1] = c.sh, r[2] = c.ip, r[3] = c.tl, r[4] = c.l4;
-        r[6] = (uint32_t)first, r[7] = (uint32_t)(first >> 32);
-    }
-    __syncthreads();
-    if (tid == 0)
-    {
-        uint32_t t[5];
-        uint64_t mn = ~0ull;
-        for (uint32_t k = 0; k < 5; ++k)
-        {
-            t[k] = 0;
-            for (uint32_t w = 0; w < NWV; ++w)
-                t[k] += s_cnt[w][k];
-        }
-        for (uint32_t w = 0; w < NWV; ++w)
-        {
-            const uint64_t m = s_cnt[w][6] | (uint64_t)s_cnt[w][7] << 32;
-            mn = m < mn ? m : mn;
-        }
-        pb_vrecord(A.rec, blockIdx.x, t[0], t[1], t[2], t[3], t[4], mn);
-    }
+    pb_tally_finish<5, NWV>(c, A.rec, s_cnt);
 }
 
-// The workgroups' records folded by one workgroup into mapped pinned host memory (as pb_ctr_read
-// does): out = {bad, short, ip, tot_len, l4, first bad}
+// The workgroups' records of N counts folded by one workgroup into mapped pinned host memory (as
+// pb_ctr_read does): out = the N counts in the record's order, then the first bad index
+template <int N>
 __global__ __launch_bounds__(256) void pb_vfold_kernel(const uint32_t *rec, uint32_t nrec, unsigned long long *out)
 {
-    uint64_t t[5] = {0, 0, 0, 0, 0}, mn = ~0ull;
+    uint64_t t[N] = {}, mn = ~0ull;
     for (uint32_t i = threadIdx.x; i < nrec; i += 256u)
     {
-        const pb_u32x4 *r = reinterpret_cast<const pb_u32x4 *>(rec + (size_t)i * PB_VREC_DW);
-        const pb_u32x4 a = r[0], b = r[1];
-        t[0] += a.x, t[1] += a.y, t[2] += a.z, t[3] += a.w, t[4] += b.x;
-        const uint64_t m = b.z | (uint64_t)b.w << 32;
+        const pb_u32x4 *r = reinterpret_cast<const pb_u32x4 *>(rec + (size_t)i * PB_REC_DW(N));
+        uint32_t d[PB_REC_DW(N)];
+#pragma unroll
+        for (int k = 0; k < PB_REC_DW(N) / 4; ++k)
+        {
+            const pb_u32x4 v = r[k];
+            d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            t[k] += d[k];
+        const uint64_t m = d[N] | (uint64_t)d[N + 1] << 32;
         mn = m < mn ? m : mn;
     }
 #pragma unroll
     for (uint32_t dd = 32; dd > 0; dd >>= 1)
 #pragma unroll
-        for (uint32_t k = 0; k < 5; ++k)
+        for (int k = 0; k < N; ++k)
             t[k] += __shfl_xor(t[k], dd, 64);
     mn = pb_vwave_min(mn);
-    __shared__ unsigned long long s_t[4][6];
+    __shared__ unsigned long long s_t[4][N + 1];
     if ((threadIdx.x & 63u) == 0)
     {
-        for (uint32_t k = 0; k < 5; ++k)
+#pragma unroll
+        for (int k = 0; k < N; ++k)
             s_t[threadIdx.x >> 6][k] = t[k];
-        s_t[threadIdx.x >> 6][5] = mn;
+        s_t[threadIdx.x >> 6][N] = mn;
     }
     __syncthreads();
     if (threadIdx.x == 0)
     {
-        for (uint32_t k = 0; k < 5; ++k)
+        for (int k = 0; k < N; ++k)
             out[k] = s_t[0][k] + s_t[1][k] + s_t[2][k] + s_t[3][k];
         for (uint32_t w = 1; w < 4; ++w)
-            mn = s_t[w][5] < mn ? s_t[w][5] : mn;
-        out[5] = mn;
+            mn = s_t[w][N] < mn ? s_t[w][N] : mn;
+        out[N] = mn;
     }
 }
 
@@ -4167,9 +4286,16 @@ extern "C" hipError_t pbk_launch_verify(const pb_vargs *A, int shape, uint32_t g
     return hipGetLastError();
 }
 
-extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st)
+// ncnt: the counts of a record, 5 (pbgpu_verify) or 11 (pbgpu_verify_wire)
+extern "C" hipError_t pbk_launch_vfold(const uint32_t *rec, uint32_t nrec, uint32_t ncnt, unsigned long long *out,
+                                       hipStream_t st)
 {
-    hipLaunchKernelGGL(pb_vfold_kernel, dim3(1), dim3(256), 0, st, rec, nrec, out);
+    if (ncnt == 5)
+        hipLaunchKernelGGL(pb_vfold_kernel<5>, dim3(1), dim3(256), 0, st, rec, nrec, out);
+    else if (ncnt == 11)
+        hipLaunchKernelGGL(pb_vfold_kernel<11>, dim3(1), dim3(256), 0, st, rec, nrec, out);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -4370,32 +4496,18 @@ __device__ __forceinline__ uint2 pb_wire_parse(const uint32_t *dw, uint32_t hb, 
     return make_uint2(code | lo0 << 16 | lo1 << 24, ps0 | ps1 << 16);
 }
 
-// a wave's tallies (the counts are wave-uniform, first is per lane); code: PB_W_* included
-struct pb_wcount
+// code: PB_W_* included
+struct pb_w_kind
 {
-    uint32_t c[11]; // bad, malformed, l3 csum, l3 len, l4 csum, udp len, ipv4, ipv6, inner, nol4, other
-    uint64_t first;
-};
-
-__device__ __forceinline__ void pb_wtally(pb_wcount &c, bool lead, uint32_t code, uint64_t f)
-{
-    if (__ballot(lead && (code & 31u))) // wave-uniform: clean frames skip the failure counts
+    // bad, malformed, l3 csum, l3 len, l4 csum, udp len | ipv4, ipv6, inner, nol4, other
+    static constexpr int N = 11, NF = 6;
+    static constexpr bool SKIP = true;
+    static __device__ __forceinline__ constexpr uint32_t mask(int k)
     {
-        c.c[0] += (uint32_t)__popcll(__ballot(lead && (code & 31u)));
-        c.c[1] += (uint32_t)__popcll(__ballot(lead && (code & 16u)));
-        c.c[2] += (uint32_t)__popcll(__ballot(lead && (code & 1u)));
-        c.c[3] += (uint32_t)__popcll(__ballot(lead && (code & 2u)));
-        c.c[4] += (uint32_t)__popcll(__ballot(lead && (code & 4u)));
-        c.c[5] += (uint32_t)__popcll(__ballot(lead && (code & 8u)));
-        if (lead && (code & 31u) && f < c.first)
-            c.first = f;
+        constexpr uint32_t m[N] = {31u, 16u, 1u, 2u, 4u, 8u, PB_W_V4, PB_W_V6, 64u, 32u, 128u};
+        return m[k];
     }
-    c.c[6] += (uint32_t)__popcll(__ballot(lead && (code & PB_W_V4)));
-    c.c[7] += (uint32_t)__popcll(__ballot(lead && (code & PB_W_V6)));
-    c.c[8] += (uint32_t)__popcll(__ballot(lead && (code & 64u)));
-    c.c[9] += (uint32_t)__popcll(__ballot(lead && (code & 32u)));
-    c.c[10] += (uint32_t)__popcll(__ballot(lead && (code & 128u)));
-}
+};
 
 template <int G, bool CODES>
 __global__ __launch_bounds__(PB_VST_WT) void pb_wire_kernel(pb_wargs A)
@@ -4409,55 +4521,29 @@ __global__ __launch_bounds__(PB_VST_WT) void pb_wire_kernel(pb_wargs A)
     const uint32_t tid = threadIdx.x, grp = tid / G, gl = tid % G;
     const uint64_t fa = (uint64_t)pb_xcd_region(blockIdx.x, gridDim.x) * A.wgf;
     const uint64_t fe = fa + A.wgf < A.n ? fa + A.wgf : A.n;
-    pb_wcount c = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ~0ull};
+    pb_tally<11> c = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ~0ull};
     for (uint64_t w0 = fa; w0 < fe; w0 += A.bf)
     {
-        const uint32_t wn = fe - w0 < A.bf ? (uint32_t)(fe - w0) : A.bf;
-        const uint64_t g0 = A.first + w0;
-        const uint64_t sb = A.offsets ? A.offsets[g0] : g0 * A.fixed_len;
-        const uint64_t eb = A.offsets ? A.offsets[g0 + wn] : (g0 + wn) * A.fixed_len;
-        const uint64_t s16 = sb & ~15ull;
-        const bool staged = eb - s16 <= PB_VS_STAGE;
-        const uint32_t span16 = (uint32_t)((eb - s16 + 15ull) & ~15ull); // < 2^26: bf frames of < 64 KiB
-        const uint8_t *src = A.data + s16;
-        if (w0 != fa)
-            __syncthreads(); // the previous window has been summed
-        for (uint32_t i = tid; i <= wn; i += PB_VST_WT)
-            s_off[i] = (uint32_t)((A.offsets ? A.offsets[g0 + i] : (g0 + i) * A.fixed_len) - s16);
-        if (staged)
-            for (uint32_t ch = tid; ch < (span16 >> 4); ch += PB_VST_WT)
-                s_stage[ch] = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
-        __syncthreads();
-        if (staged)
+        const pb_vs_win W = pb_vs_window(A, w0, fa, fe, s_stage, s_off);
+        if (W.staged)
         {
             // parse stage: one lane per frame of the window
-            for (uint32_t i = tid; i < wn; i += PB_VST_WT)
+            for (uint32_t i = tid; i < W.wn; i += PB_VST_WT)
                 s_desc[i] = pb_wire_parse(dw, s_off[i], s_off[i + 1u] - s_off[i], A.port, A.checks);
             __syncthreads();
         }
-        for (uint32_t r0 = 0; r0 < wn; r0 += NG)
+        for (uint32_t r0 = 0; r0 < W.wn; r0 += NG)
         {
             const uint32_t fi = r0 + grp;
-            const bool valid = fi < wn;
+            const bool valid = fi < W.wn;
             const uint32_t p = s_off[valid ? fi : 0u], q = s_off[valid ? fi + 1u : 0u];
-            if (!staged)
+            if (!W.staged)
             {
                 // the frame's first fourteen chunks (every header byte lies in its first 200 bytes) into
-                // the group's 224-B slot, parsed by the group's first lane (a group is inside one wave)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                for (uint32_t k = gl; k < 14u; k += G)
-                {
-                    const uint32_t cb = (p & ~15u) + 16u * k;
-                    s_stage[grp * 14u + k] =
-                        cb < span16 ? *reinterpret_cast<const pb_u32x4 *>(src + cb) : pb_u32x4{0, 0, 0, 0};
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // the group's 224-B slot, parsed by the group's first lane
+                const uint32_t hb = pb_vs_head<G, 14>(W, s_stage, grp, gl, p);
                 if (valid && gl == 0u)
-                    s_desc[fi] = pb_wire_parse(dw, grp * 224u + (p & 15u), q - p, A.port, A.checks);
+                    s_desc[fi] = pb_wire_parse(dw, hb, q - p, A.port, A.checks);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -4467,48 +4553,13 @@ __global__ __launch_bounds__(PB_VST_WT) void pb_wire_kernel(pb_wargs A)
             uint32_t acc0 = 0, acc1 = 0;
             if (valid && r0lo)
             {
-                const uint32_t lo = p + r0lo, hi = q; // hi > lo: an L4 header fits
-                const uint32_t c0 = lo >> 4, c1 = (hi - 1u) >> 4;
                 // Range 1 is there only for a VXLAN frame whose outer UDP checksum is not 00 00: the outer
                 // range then contains the inner one, and the inner bytes are added to both sums from the one
                 // load.  No pipeline of this generator produces that case (pbgpu_encap writes 00 00); it comes
                 // from uploads only.
-                const uint32_t lo1 = p + r1lo, c0b = r1lo ? lo1 >> 4 : ~0u;
-                for (uint32_t ch = c0 + gl; ch <= c1; ch += G)
-                {
-                    pb_u32x4 v;
-                    if (staged)
-                        v = s_stage[ch];
-                    else
-                        v = *reinterpret_cast<const pb_u32x4 *>(src + 16u * ch);
-                    if (ch == c0 || ch == c1)
-                    {
-                        const int a = (int)lo - (int)(16u * ch), b = (int)hi - (int)(16u * ch);
-                        v.x &= pb_bytemask(a, b, 0);
-                        v.y &= pb_bytemask(a, b, 1);
-                        v.z &= pb_bytemask(a, b, 2);
-                        v.w &= pb_bytemask(a, b, 3);
-                    }
-                    acc0 = pb_add_halves(acc0, v.x);
-                    acc0 = pb_add_halves(acc0, v.y);
-                    acc0 = pb_add_halves(acc0, v.z);
-                    acc0 = pb_add_halves(acc0, v.w);
-                    if (ch >= c0b)
-                    {
-                        if (ch == c0b)
-                        {
-                            const int a = (int)lo1 - (int)(16u * ch);
-                            v.x &= pb_bytemask(a, 16, 0);
-                            v.y &= pb_bytemask(a, 16, 1);
-                            v.z &= pb_bytemask(a, 16, 2);
-                            v.w &= pb_bytemask(a, 16, 3);
-                        }
-                        acc1 = pb_add_halves(acc1, v.x);
-                        acc1 = pb_add_halves(acc1, v.y);
-                        acc1 = pb_add_halves(acc1, v.z);
-                        acc1 = pb_add_halves(acc1, v.w);
-                    }
-                }
+                const uint32_t lo1 = p + r1lo;
+                // q > p + r0lo: an L4 header fits
+                pb_vs_sum<G, true>(W, s_stage, gl, p + r0lo, q, lo1, r1lo ? lo1 >> 4 : ~0u, acc0, acc1);
             }
             acc0 = pb_group_sum<G>(acc0);
             acc1 = pb_group_sum<G>(acc1);
@@ -4521,84 +4572,12 @@ __global__ __launch_bounds__(PB_VST_WT) void pb_wire_kernel(pb_wargs A)
                 code |= 4u & A.checks;
             if (lead && r1lo && pb_fold(seg1 + (d.y >> 16)) != 0xFFFFu)
                 code |= 4u & A.checks;
-            pb_wtally(c, lead, code, g0 + fi);
+            pb_tally_add<pb_w_kind>(c, lead, code, W.g0 + fi);
             if (CODES && lead)
                 A.codes[w0 + fi] = (uint8_t)code;
         }
     }
-    const uint64_t first = pb_vwave_min(c.first);
-    if ((tid & 63u) == 0)
-    {
-        uint32_t *r = s_cnt[tid >> 6];
-#pragma unroll
-        for (uint32_t k = 0; k < 11u; ++k)
-            r[k] = c.c[k];
-        r[12] = (uint32_t)first, r[13] = (uint32_t)(first >> 32);
-    }
-    __syncthreads();
-    if (tid == 0)
-    {
-        uint32_t t[11];
-        uint64_t mn = ~0ull;
-#pragma unroll
-        for (uint32_t k = 0; k < 11u; ++k)
-        {
-            t[k] = 0;
-            for (uint32_t w = 0; w < NWV; ++w)
-                t[k] += s_cnt[w][k];
-        }
-        for (uint32_t w = 0; w < NWV; ++w)
-        {
-            const uint64_t m = s_cnt[w][12] | (uint64_t)s_cnt[w][13] << 32;
-            mn = m < mn ? m : mn;
-        }
-        // the workgroup's record: four plain 16-B stores
-        pb_u32x4 *r = reinterpret_cast<pb_u32x4 *>(A.rec + (size_t)blockIdx.x * PB_WREC_DW);
-        r[0] = pb_u32x4{t[0], t[1], t[2], t[3]};
-        r[1] = pb_u32x4{t[4], t[5], t[6], t[7]};
-        r[2] = pb_u32x4{t[8], t[9], t[10], 0u};
-        r[3] = pb_u32x4{(uint32_t)mn, (uint32_t)(mn >> 32), 0u, 0u};
-    }
-}
-
-// The workgroups' records folded by one workgroup into mapped pinned host memory, as pb_vfold_kernel
-// does: out = the eleven counts in the record's order, then the first bad index
-__global__ __launch_bounds__(256) void pb_wfold_kernel(const uint32_t *rec, uint32_t nrec, unsigned long long *out)
-{
-    uint64_t t[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mn = ~0ull;
-    for (uint32_t i = threadIdx.x; i < nrec; i += 256u)
-    {
-        const pb_u32x4 *r = reinterpret_cast<const pb_u32x4 *>(rec + (size_t)i * PB_WREC_DW);
-        const pb_u32x4 a = r[0], b = r[1], cc = r[2], d = r[3];
-        t[0] += a.x, t[1] += a.y, t[2] += a.z, t[3] += a.w;
-        t[4] += b.x, t[5] += b.y, t[6] += b.z, t[7] += b.w;
-        t[8] += cc.x, t[9] += cc.y, t[10] += cc.z;
-        const uint64_t m = d.x | (uint64_t)d.y << 32;
-        mn = m < mn ? m : mn;
-    }
-#pragma unroll
-    for (uint32_t dd = 32; dd > 0; dd >>= 1)
-#pragma unroll
-        for (uint32_t k = 0; k < 11; ++k)
-            t[k] += __shfl_xor(t[k], dd, 64);
-    mn = pb_vwave_min(mn);
-    __shared__ unsigned long long s_t[4][12];
-    if ((threadIdx.x & 63u) == 0)
-    {
-#pragma unroll
-        for (uint32_t k = 0; k < 11; ++k)
-            s_t[threadIdx.x >> 6][k] = t[k];
-        s_t[threadIdx.x >> 6][11] = mn;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        for (uint32_t k = 0; k < 11; ++k)
-            out[k] = s_t[0][k] + s_t[1][k] + s_t[2][k] + s_t[3][k];
-        for (uint32_t w = 1; w < 4; ++w)
-            mn = s_t[w][11] < mn ? s_t[w][11] : mn;
-        out[11] = mn;
-    }
+    pb_tally_finish<11, NWV>(c, A.rec, s_cnt);
 }
 
 // G: lanes per frame (8, 16, 32, 64)
@@ -4619,12 +4598,6 @@ extern "C" hipError_t pbk_launch_wire(const pb_wargs *A, int G, uint32_t grid, h
     default: return hipErrorInvalidValue;
     }
 #undef PBK_WIRE
-    return hipGetLastError();
-}
-
-extern "C" hipError_t pbk_launch_wfold(const uint32_t *rec, uint32_t nrec, unsigned long long *out, hipStream_t st)
-{
-    hipLaunchKernelGGL(pb_wfold_kernel, dim3(1), dim3(256), 0, st, rec, nrec, out);
     return hipGetLastError();
 }
 
@@ -4753,6 +4726,82 @@ __device__ __forceinline__ void pb_rp_next_page(int32_t &d0, uint64_t &j0, const
     j0 += kn;
 }
 
+// The page walk of the writers whose record j is source frame first + j with `add` bytes inserted
+// (pb_pcap_kernel, pb_encap_kernel, pb_xlat_kernel; pb_cut_write's window comes from its map).
+struct pb_rp_walk
+{
+    uint64_t p;     // the page's first byte in the output
+    uint64_t j0;    // the record holding the first page's first byte, then (variable length) the window's
+                    // first record or (fixed length) the record holding the page's first byte
+    int32_t d0;     // the page's first byte's offset in record j0
+    uint64_t offj0; // variable length: frame first + j0's offset in src
+    uint64_t fj0;   // fixed length: the same
+    uint32_t kw;    // SLOTS: the window's index of the record holding the page's first byte
+    bool have_win;
+};
+
+// q0: the first page's first byte counted from record 0's first byte (pcap: below 0 inside the file
+// header, which counts as record 0's bytes before its start)
+template <bool VAR>
+__device__ __forceinline__ void pb_rp_walk_begin(pb_rp_walk &W, uint64_t p, int64_t q0, const uint64_t *offsets,
+                                                 uint64_t first, uint64_t n, uint32_t add, uint32_t reclen)
+{
+    uint64_t g0 = 0;
+    W.p = p;
+    W.j0 = 0;
+    if (q0 > 0)
+        pb_rp_first<VAR>(offsets, first, n, add, reclen, (uint64_t)q0, W.j0, g0);
+    W.d0 = (int32_t)(q0 - (int64_t)g0);
+    W.offj0 = 0;
+    W.have_win = false;
+}
+
+// Before a page's lanes look at it.  Variable length: the window of WIN record positions is kept
+// from page to page (d0 then grows by 4096 a page) and moved to the record holding the page's first
+// byte only when it no longer reaches the record after the page's last byte; moved there it always
+// does (WIN).  SLOTS: the caller stages per-page slots in LDS after this, so every page begins with
+// a barrier (the last page's slot readers are done) and kw is found.
+template <bool VAR, bool SLOTS, uint32_t WIN, uint32_t WT>
+__device__ __forceinline__ void pb_rp_walk_page(pb_rp_walk &W, uint32_t *s_rel, const uint64_t *offsets,
+                                                uint64_t first, uint64_t n, uint32_t fixed_len, uint32_t add)
+{
+    W.kw = 0;
+    if (VAR)
+    {
+        const bool move = !W.have_win || (int64_t)s_rel[WIN - 1u] <= (int64_t)W.d0 + 4095;
+        if (move)
+        {
+            if (W.have_win) // d0 is inside the window
+            {
+                const uint32_t lo = pb_rp_find(s_rel, (uint32_t)W.d0, 0u, WIN - 1u);
+                W.j0 += lo;
+                W.d0 -= (int32_t)s_rel[lo];
+            }
+            __syncthreads(); // the window's readers are done
+            W.offj0 = pb_rp_refill(s_rel, WIN, WT, offsets, first, n, add, W.j0);
+            W.have_win = true;
+        }
+        if (SLOTS || move)
+            __syncthreads(); // the window is in place
+        if (SLOTS)
+            W.kw = pb_rp_find(s_rel, (uint32_t)W.d0, 0u, WIN - 1u);
+    }
+    else if (SLOTS)
+        __syncthreads();
+    W.fj0 = VAR ? 0 : (first + W.j0) * fixed_len;
+}
+
+// the next page's first byte: 4096 on in the same window, or a whole number of records on
+template <bool VAR>
+__device__ __forceinline__ void pb_rp_walk_next(pb_rp_walk &W, const pb_div &rec, uint32_t reclen)
+{
+    W.p += 4096u;
+    if (VAR)
+        W.d0 += 4096;
+    else
+        pb_rp_next_page(W.d0, W.j0, rec, reclen);
+}
+
 // Frame first + j of a range: its first byte o in the buffer and its length L, from offsets[]
 // (var) or the fixed length; with ob, also the range's first byte
 __device__ __forceinline__ void pb_rp_frame(const uint64_t *offsets, uint64_t first, uint32_t fixed_len, bool var,
@@ -4860,38 +4909,18 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
     const uint32_t tid = threadIdx.x;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
     const uint32_t reclen = A.fixed_len + 16u;
-    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the stream
-    if (p >= A.end16)
+    const uint64_t p0 = ((uint64_t)blockIdx.x * A.per) << 12; // the first page's first byte in the stream
+    if (p0 >= A.end16)
         return;
-    // j0: the record holding the first page's first byte (0 while that byte is in the file header),
-    // d0: that byte's offset in the record
-    const int64_t q0 = (int64_t)p - (int64_t)A.hdr;
-    uint64_t j0 = 0, g0 = 0;
-    if (q0 > 0)
-        pb_rp_first<VAR>(A.offsets, A.first, A.n, 16u, reclen, (uint64_t)q0, j0, g0);
-    int32_t d0 = (int32_t)(q0 - (int64_t)g0);
-    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
-    bool have_win = false;
-    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    // j0 is 0 while the page's first byte is in the file header
+    pb_rp_walk W;
+    pb_rp_walk_begin<VAR>(W, p0, (int64_t)p0 - (int64_t)A.hdr, A.offsets, A.first, A.n, 16u, reclen);
+    for (uint32_t it = 0; it < A.per && W.p < A.end16; ++it, pb_rp_walk_next<VAR>(W, A.rec, reclen))
     {
-        // variable length: the window of record positions is kept from page to page (d0 then grows
-        // by 4096 a page) and moved only when it no longer reaches the record after the page's last
-        // byte; moved to the record holding the page's first byte it always does (PB_PC_WIN)
-        if (VAR && (!have_win || (int64_t)s_rel[PB_PC_WIN - 1u] <= (int64_t)d0 + 4095))
-        {
-            if (have_win) // d0 >= 4096 - 24 here, and inside the window
-            {
-                const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_PC_WIN - 1u);
-                j0 += lo;
-                d0 -= (int32_t)s_rel[lo];
-            }
-            __syncthreads(); // the window's readers are done
-            offj0 = pb_rp_refill(s_rel, PB_PC_WIN, PB_PC_WT, A.offsets, A.first, A.n, 16u, j0);
-            __syncthreads();
-            have_win = true;
-        }
-        const int32_t d = d0 + 16 * (int32_t)tid;
-        const uint64_t pc = p + 16u * tid;
+        pb_rp_walk_page<VAR, false, PB_PC_WIN, PB_PC_WT>(W, s_rel, A.offsets, A.first, A.n, A.fixed_len, 16u);
+        const uint64_t j0 = W.j0, offj0 = W.offj0;
+        const int32_t d = W.d0 + 16 * (int32_t)tid;
+        const uint64_t pc = W.p + 16u * tid;
         if (pc < A.end16)
         {
             // k, r: the chunk starts r bytes into record j0 + k
@@ -4981,11 +5010,6 @@ __global__ __launch_bounds__(PB_PC_WT) void pb_pcap_kernel(pb_pcargs A)
             }
             *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
         }
-        // the next page's first byte: 4096 on in the same window, or a whole number of records on
-        if (VAR)
-            d0 += 4096;
-        else
-            pb_rp_next_page(d0, j0, A.rec, reclen);
     }
 }
 
@@ -5011,65 +5035,49 @@ extern "C" hipError_t pbk_launch_pcap(const pb_pcargs *A, uint32_t grid, hipStre
 // headers, and three byte masks per dword that select among them.  A wave none of whose chunks
 // touches a header takes a plain shifted copy instead; the choice is per wave, never per lane.
 
-template <bool VAR>
-__global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
+// The writer exists once, as a template over a kind (pb_en_kind here, pb_xl_kind with pbgpu_xlat46),
+// which supplies
+//   args, WT            its argument block and threads per workgroup
+//   WIN, HREC           the window's records and the header slots per page
+//   TN                  dwords of a header as built: the staged ones and a zero one behind them
+//   add(), split()      the bytes a record is longer than its frame, and where in the frame they go
+//                       (SPLIT false: always 0, the leading-source gather is not compiled)
+//   hdw(), stride()     the staged dwords of a slot, and a slot's dwords
+//   UNIFORM             the staged length is add for every record (else it is kept per record in
+//                       the slot's dword TN)
+//   header()            a record's header built into T[], from the frame at `so` of L bytes;
+//                       returns the staged length
+// A record's bytes: [0, S) source, [S, S + staged length) the slot, then source `add` bytes back.
+template <class KIND, bool VAR>
+__device__ __forceinline__ void pb_ins_write(const typename KIND::args &A, uint32_t *s_rel, uint32_t *s_hdr)
 {
-    // variable length: output positions of PB_EN_WIN records from record j0 on, relative to it
-    // (below 258 * 65535); 0xFFFFFFFF past the end of the range
-    __shared__ uint32_t s_rel[PB_EN_WIN];
-    // slot i: the header of the i-th record touching the page, A.hdw dwords
-    __shared__ uint32_t s_hdr[PB_EN_HREC * PB_EN_HDW];
+    constexpr uint32_t WIN = KIND::WIN;
     const uint32_t tid = threadIdx.x;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-    const uint32_t P = A.P, hdw = A.hdw;
-    const int32_t S = (int32_t)A.split;
-    const uint32_t reclen = A.fixed_len + P;
-    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
-    if (p >= A.end16)
+    const uint32_t add = KIND::add(A), hdw = KIND::hdw(A), stride = KIND::stride(A);
+    const int32_t S = (int32_t)KIND::split(A);
+    const uint32_t reclen = A.fixed_len + add;
+    const uint64_t p0 = ((uint64_t)blockIdx.x * A.per) << 12; // the first page's first byte in the output
+    if (p0 >= A.end16)
         return;
-    // j0: the record holding the first page's first byte, d0: that byte's offset in the record
-    uint64_t j0 = 0, g0 = 0;
-    if (p > 0)
-        pb_rp_first<VAR>(A.offsets, A.first, A.n, P, reclen, p, j0, g0);
-    int32_t d0 = (int32_t)(p - g0);
-    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
-    bool have_win = false;
-    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
+    pb_rp_walk W;
+    pb_rp_walk_begin<VAR>(W, p0, (int64_t)p0, A.offsets, A.first, A.n, add, reclen);
+    for (uint32_t it = 0; it < A.per && W.p < A.end16; ++it, pb_rp_walk_next<VAR>(W, A.rec, reclen))
     {
-        // variable length: the window is kept from page to page (d0 then grows by 4096 a page) and
-        // moved to the record holding the page's first byte only when it no longer reaches the
-        // record after the page's last byte
-        uint32_t kw = 0; // the window's index of the record holding the page's first byte
-        if (VAR)
-        {
-            if (!have_win || (int64_t)s_rel[PB_EN_WIN - 1u] <= (int64_t)d0 + 4095)
-            {
-                if (have_win)
-                {
-                    const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_EN_WIN - 1u);
-                    j0 += lo;
-                    d0 -= (int32_t)s_rel[lo];
-                }
-                __syncthreads(); // the window's readers are done
-                offj0 = pb_rp_refill(s_rel, PB_EN_WIN, PB_EN_WT, A.offsets, A.first, A.n, P, j0);
-                have_win = true;
-            }
-            __syncthreads(); // the window is in place, the last page's header readers are done
-            kw = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_EN_WIN - 1u);
-        }
-        else
-            __syncthreads(); // the last page's header readers are done
-        const uint64_t fj0 = VAR ? 0 : (A.first + j0) * A.fixed_len; // fixed length: frame first + j0's offset in src
+        pb_rp_walk_page<VAR, true, WIN, KIND::WT>(W, s_rel, A.offsets, A.first, A.n, A.fixed_len, add);
+        const uint64_t j0 = W.j0, offj0 = W.offj0, fj0 = W.fj0;
+        const int32_t d0 = W.d0;
+        const uint32_t kw = W.kw;
 
         // ---- header stage: lane i stages the header of the i-th record touching the page ----
-        if (tid < PB_EN_HREC)
+        if (tid < KIND::HREC)
         {
             const uint32_t k = kw + tid;
             bool act;
             uint32_t rs = 0, rlen = reclen; // the record's start relative to record j0, its length
             if (VAR)
             {
-                act = k + 1u < PB_EN_WIN;
+                act = k + 1u < WIN;
                 if (act)
                 {
                     rs = s_rel[k];
@@ -5085,53 +5093,22 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             }
             if (act && (int64_t)rs < (int64_t)d0 + 4096)
             {
-                const uint32_t L = rlen - P;
-                uint32_t T[PB_EN_TDW + 1u];
-#pragma unroll
-                for (uint32_t u = 0; u < PB_EN_TDW; ++u)
-                    T[u] = A.tpl[u];
-                T[PB_EN_TDW] = 0u;
-                if (VAR && (A.flags & PB_EN_VXLAN))
-                {
-                    // tot_len (bytes 16-17), the IPv4 checksum (24-25: the constant words + tot_len,
-                    // folded) and the UDP length (38-39)
-                    const uint32_t tot = L + 36u;
-                    const uint32_t c = ~pb_fold(A.csum_base + tot) & 0xFFFFu;
-                    T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
-                    T[6] = (T[6] & 0xFFFF0000u) | pb_bswap16(c);
-                    T[9] = (T[9] & 0x0000FFFFu) | (pb_bswap16(L + 16u) << 16);
-                }
-                if (A.flags & PB_EN_HASH)
-                {
-                    // source bytes 26..37 as aligned dwords; bytes past the frame count as 0
-                    const uint64_t so = VAR ? offj0 + (rs - P * k) : fj0 + (uint64_t)k * A.fixed_len;
-                    const uint64_t a = so + 26u, end = so + L;
-                    const uint64_t i = a >> 2;
-                    const uint32_t sh = (uint32_t)a & 3u;
-                    uint32_t d[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
-                    const int32_t vb = (int32_t)L - 26; // bytes of the twelve inside the frame
-                    uint32_t x = 0;
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-                        x ^= __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh) & pb_rp_lt(4 * t, vb);
-                    x ^= x >> 16;
-                    x *= 0x7FEB352Du;
-                    x ^= x >> 15;
-                    const uint32_t sport = 49152u + (x & 0x3FFFu);
-                    T[8] = (T[8] & 0x0000FFFFu) | (pb_bswap16(sport) << 16); // bytes 34-35
-                }
+                const uint32_t L = rlen - add;
+                const uint64_t so = VAR ? offj0 + (rs - add * k) : fj0 + (uint64_t)k * A.fixed_len;
+                uint32_t T[KIND::TN];
+                const uint32_t sl = KIND::template header<VAR>(A, w, so, L, T);
                 const int32_t hs = (int32_t)rs + S - d0; // the header's first byte in the page (below 0: before it)
-                pb_rp_stage(s_hdr + tid * hdw, T, hdw, (uint32_t)hs & 3u);
+                uint32_t *slot = s_hdr + tid * stride;
+                pb_rp_stage(slot, T, hdw, (uint32_t)hs & 3u);
+                if (!KIND::UNIFORM)
+                    slot[KIND::TN] = sl;
             }
         }
         __syncthreads();
 
         // ---- chunks ----
         const int32_t d = d0 + 16 * (int32_t)tid;
-        const uint64_t pc = p + 16u * tid;
+        const uint64_t pc = W.p + 16u * tid;
         if (pc < A.end16)
         {
             // k, r: the chunk starts r bytes into record j0 + k, which is ea bytes long; pc is
@@ -5139,7 +5116,7 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             uint32_t k, rs, ea;
             if (VAR)
             {
-                k = pb_rp_find(s_rel, (uint32_t)d, 0u, PB_EN_WIN - 1u);
+                k = pb_rp_find(s_rel, (uint32_t)d, 0u, WIN - 1u);
                 rs = s_rel[k];
                 ea = s_rel[k + 1u] - rs;
             }
@@ -5151,29 +5128,29 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
             }
             const int32_t r = d - (int32_t)rs;
             const bool bvalid = j0 + k + 1u < A.n; // a next record: its first bytes may end the chunk
-            const int64_t offa = (int64_t)(VAR ? offj0 + (rs - P * k) : fj0 + (uint64_t)k * A.fixed_len);
-            // the record's bytes: [0, S) source, [S, S + P) header, [S + P, e3) source P bytes back
+            const int64_t offa = (int64_t)(VAR ? offj0 + (rs - add * k) : fj0 + (uint64_t)k * A.fixed_len);
+            const uint32_t ia = k - kw; // the record's header slot; the next record's is the one after
+            // the record's bytes: [0, S) source, [S, sp) header, [sp, e3) source `add` bytes back
             // (through the next record's first S bytes: frames are packed), from e3 the next header
             // or, past the range, zeros
-            const int32_t sp = S + (int32_t)P;
+            const int32_t sp = S + (int32_t)(KIND::UNIFORM ? add : s_hdr[ia * stride + KIND::TN]);
             const int32_t e3 = bvalid ? (int32_t)ea + S : (int32_t)ea;
             pb_u32x4 v;
             // A wave whose chunks all lie wholly in source bytes behind their record's header (two waves
             // of three at 1500 B) copies (a fifth dword still holds a byte of the frame).  Decided per
             // wave, so no lane waits for another's path.
             if (__ballot(!(r >= sp && r + 16 <= e3)) == 0ull)
-                v = pb_rp_copy16(w, (uint64_t)(offa + r - (int32_t)P)); // at or after the frame's byte S
+                v = pb_rp_copy16(w, (uint64_t)(offa + r - (int32_t)add)); // at or after the frame's byte S
             else
             {
                 uint32_t s0[4] = {0u, 0u, 0u, 0u}, s1[4];
                 {
                     const int32_t lo = (r > sp ? r : sp) - r;
                     const int32_t hi = (r + 16 < e3 ? r + 16 : e3) - r;
-                    pb_rp_gather(w, offa + r - (int32_t)P, lo, hi, s1);
+                    pb_rp_gather(w, offa + r - (int32_t)add, lo, hi, s1);
                 }
-                if (S)
+                if (KIND::SPLIT && S)
                     pb_rp_gather(w, offa + r, 0, S - r, s0);
-                const uint32_t ia = k - kw; // the record's header slot; the next record's is the one after
                 const int32_t hsa = (int32_t)rs + S - d0, hsb = hsa + (int32_t)ea;
                 const int32_t q = 16 * (int32_t)tid;
                 const int32_t ua = (q - (hsa & ~3)) >> 2, ub = (q - (hsb & ~3)) >> 2;
@@ -5181,23 +5158,85 @@ __global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
                 {
-                    const uint32_t va = (uint32_t)(ua + t) < hdw ? s_hdr[ia * hdw + (uint32_t)(ua + t)] : 0u;
+                    const uint32_t va = (uint32_t)(ua + t) < hdw ? s_hdr[ia * stride + (uint32_t)(ua + t)] : 0u;
                     const uint32_t vb =
-                        bvalid && (uint32_t)(ub + t) < hdw ? s_hdr[(ia + 1u) * hdw + (uint32_t)(ub + t)] : 0u;
+                        bvalid && (uint32_t)(ub + t) < hdw ? s_hdr[(ia + 1u) * stride + (uint32_t)(ub + t)] : 0u;
                     const int32_t o = r + 4 * t;
-                    const uint32_t m1 = pb_rp_lt(o, S), m2 = pb_rp_lt(o, sp), m3 = pb_rp_lt(o, e3);
+                    const uint32_t m1 = KIND::SPLIT ? pb_rp_lt(o, S) : 0u, m2 = pb_rp_lt(o, sp), m3 = pb_rp_lt(o, e3);
                     o4[t] = (s0[t] & m1) | (va & m2 & ~m1) | (s1[t] & m3 & ~m2) | (vb & ~m3);
                 }
                 v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
             }
             *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
         }
-        // the next page's first byte: 4096 on in the same window, or a whole number of records on
-        if (VAR)
-            d0 += 4096;
-        else
-            pb_rp_next_page(d0, j0, A.rec, reclen);
     }
+}
+
+// pbgpu_encap's kind: the template A.tpl with, per record, the VXLAN lengths and checksum (variable
+// length) and the hashed source port
+struct pb_en_kind
+{
+    typedef pb_enargs args;
+    static constexpr uint32_t WT = PB_EN_WT, WIN = PB_EN_WIN, HREC = PB_EN_HREC;
+    static constexpr uint32_t TN = PB_EN_TDW + 1u;
+    static constexpr bool SPLIT = true, UNIFORM = true;
+    static __device__ __forceinline__ uint32_t add(const pb_enargs &A) { return A.P; }
+    static __device__ __forceinline__ uint32_t split(const pb_enargs &A) { return A.split; }
+    static __device__ __forceinline__ uint32_t hdw(const pb_enargs &A) { return A.hdw; }
+    static __device__ __forceinline__ uint32_t stride(const pb_enargs &A) { return A.hdw; }
+
+    template <bool VAR>
+    static __device__ __forceinline__ uint32_t header(const pb_enargs &A, const uint32_t *w, uint64_t so, uint32_t L,
+                                                      uint32_t (&T)[TN])
+    {
+#pragma unroll
+        for (uint32_t u = 0; u < PB_EN_TDW; ++u)
+            T[u] = A.tpl[u];
+        T[PB_EN_TDW] = 0u;
+        if (VAR && (A.flags & PB_EN_VXLAN))
+        {
+            // tot_len (bytes 16-17), the IPv4 checksum (24-25: the constant words + tot_len,
+            // folded) and the UDP length (38-39)
+            const uint32_t tot = L + 36u;
+            const uint32_t c = ~pb_fold(A.csum_base + tot) & 0xFFFFu;
+            T[4] = (T[4] & 0xFFFF0000u) | pb_bswap16(tot);
+            T[6] = (T[6] & 0xFFFF0000u) | pb_bswap16(c);
+            T[9] = (T[9] & 0x0000FFFFu) | (pb_bswap16(L + 16u) << 16);
+        }
+        if (A.flags & PB_EN_HASH)
+        {
+            // source bytes 26..37 as aligned dwords; bytes past the frame count as 0
+            const uint64_t a = so + 26u, end = so + L;
+            const uint64_t i = a >> 2;
+            const uint32_t sh = (uint32_t)a & 3u;
+            uint32_t d[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
+            const int32_t vb = (int32_t)L - 26; // bytes of the twelve inside the frame
+            uint32_t x = 0;
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+                x ^= __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh) & pb_rp_lt(4 * t, vb);
+            x ^= x >> 16;
+            x *= 0x7FEB352Du;
+            x ^= x >> 15;
+            const uint32_t sport = 49152u + (x & 0x3FFFu);
+            T[8] = (T[8] & 0x0000FFFFu) | (pb_bswap16(sport) << 16); // bytes 34-35
+        }
+        return A.P;
+    }
+};
+
+template <bool VAR>
+__global__ __launch_bounds__(PB_EN_WT) void pb_encap_kernel(pb_enargs A)
+{
+    // variable length: output positions of PB_EN_WIN records from record j0 on, relative to it
+    // (below 258 * 65535); 0xFFFFFFFF past the end of the range
+    __shared__ uint32_t s_rel[PB_EN_WIN];
+    // slot i: the header of the i-th record touching the page, A.hdw dwords
+    __shared__ uint32_t s_hdr[PB_EN_HREC * PB_EN_HDW];
+    pb_ins_write<pb_en_kind, VAR>(A, s_rel, s_hdr);
 }
 
 // dst->offsets of a variable-length encapsulation: entry j = off(first + j) - off(first) + j P, j in [0, n]
@@ -5258,10 +5297,13 @@ __device__ __forceinline__ void pb_cut_read12(const uint32_t *w, uint64_t o, uin
     b20 = __builtin_amdgcn_alignbyte(d3, d2, sh);
 }
 
-__global__ __launch_bounds__(64) void pb_cut_init_kernel(unsigned long long *res)
+// the result words of a count or classify pass (cut, pbgpu_xlat46): ndw <= 64 zeros, word 4 (a
+// minimum) set to min0
+__global__ __launch_bounds__(64) void pb_res_init_kernel(unsigned long long *res, uint32_t ndw,
+                                                         unsigned long long min0)
 {
-    if (threadIdx.x < PB_FG_RES_DW)
-        res[threadIdx.x] = threadIdx.x == 4u ? 0xFFFFFFFFull : 0ull;
+    if (threadIdx.x < ndw)
+        res[threadIdx.x] = threadIdx.x == 4u ? min0 : 0ull;
 }
 
 // Count: one lane per source frame, PB_FG_CB rows of 256 frames per workgroup (one K sum per row for
@@ -5707,7 +5749,7 @@ extern "C" hipError_t pbk_launch_frag(const pb_cutargs *A, int stage, uint32_t g
     const uint32_t nblk = (uint32_t)((A->n + PB_FG_WT - 1u) / PB_FG_WT);
     if (stage == 0)
     {
-        hipLaunchKernelGGL(pb_cut_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_res_init_kernel, dim3(1), dim3(64), 0, st, A->res, PB_FG_RES_DW, 0xFFFFFFFFull);
         hipLaunchKernelGGL(pb_frag_count_kernel, dim3((nblk + PB_FG_CB - 1u) / PB_FG_CB), dim3(PB_FG_WT), 0, st, *A);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->bsum, nblk, (uint64_t *)A->res, (uint64_t)0);
     }
@@ -5915,7 +5957,7 @@ extern "C" hipError_t pbk_launch_seg(const pb_cutargs *A, int stage, int G, uint
     const uint32_t nblk = (uint32_t)((A->n + PB_FG_WT - 1u) / PB_FG_WT);
     if (stage == 0)
     {
-        hipLaunchKernelGGL(pb_cut_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_res_init_kernel, dim3(1), dim3(64), 0, st, A->res, PB_FG_RES_DW, 0xFFFFFFFFull);
         hipLaunchKernelGGL(pb_seg_count_kernel, dim3((nblk + PB_FG_CB - 1u) / PB_FG_CB), dim3(PB_FG_WT), 0, st, *A);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->bsum, nblk, (uint64_t *)A->res, (uint64_t)0);
         hipLaunchKernelGGL(pb_scan_blocks, dim3(1), dim3(1024), 0, st, A->xsum, nblk, (uint64_t *)A->res, (uint64_t)6);
@@ -6171,12 +6213,6 @@ extern "C" hipError_t pbk_launch_stamp(const pb_spargs *A, hipStream_t st)
 // L4 checksum are patched.  Two stages: classify (which frames translate; the host reads the
 // result and refuses the call before anything of dst is touched) and the destination-owned writer.
 
-__global__ __launch_bounds__(64) void pb_xlat_init_kernel(unsigned long long *res)
-{
-    if (threadIdx.x < PB_XL_RES_DW)
-        res[threadIdx.x] = threadIdx.x == 4u ? ~0ull : 0ull;
-}
-
 // Classify: one lane per frame, PB_XL_ROWS rows of 256 frames per workgroup, the four counts and the
 // lowest untranslatable index kept in registers across the rows: the result atomics come once per
 // workgroup.  A frame shorter than 34 B is never read; of the others bytes 12..23 come from aligned
@@ -6275,18 +6311,101 @@ __global__ __launch_bounds__(PB_XL_WT) void pb_xlat_class_kernel(pb_xlargs A)
     }
 }
 
-// Writer, destination-owned as pb_encap_kernel: a workgroup owns `per` consecutive 4-KiB pages of the
-// output, a lane one aligned 16-B chunk of a page per step, so every byte has one writer and every
-// store is an aligned 16-B store.  Here bytes are replaced, not only inserted (22 B by 42 B), and
-// the patched L4 bytes lie behind them, so per page one lane per
-// record touching the page stages the record's whole head in LDS: the 54 header bytes and the L4
-// bytes behind them up to the patched checksum (staged length 58 for ICMP, 62 for UDP, 72 for TCP:
-// never more than the record), at the alignment they have in the output, with the staged length in
-// the slot's last dword.  After a barrier a chunk's bytes below its record's staged length come
-// from the slot, those above it from the source 20 bytes back, and what follows the record's end
-// from the next record's slot (a record is at least 62 B: a chunk holds bytes of at most two) or,
-// past the range, zeros.  A wave whose chunks all lie behind their record's staged head takes a
-// plain shifted copy; the choice is per wave, never per lane.
+// Writer: pb_ins_write (see pbgpu_encap) with this kind.  Here bytes are replaced, not only inserted
+// (22 B by 42 B), and the patched L4 bytes lie behind them, so a record's slot holds its whole head:
+// the 54 header bytes and the L4 bytes behind them up to the patched checksum (staged length 58 for
+// ICMP, 62 for UDP, 72 for TCP: never more than the record), with the staged length in the slot's
+// last dword.  A chunk's bytes below its record's staged length come from the slot, those above it
+// from the source 20 bytes back, and what follows the record's end from the next record's slot (a
+// record is at least 62 B: a chunk holds bytes of at most two) or, past the range, zeros.
+struct pb_xl_kind
+{
+    typedef pb_xlargs args;
+    static constexpr uint32_t WT = PB_XL_WT, WIN = PB_XL_WIN, HREC = PB_XL_HREC;
+    static constexpr uint32_t TN = PB_XL_TDW;
+    static constexpr bool SPLIT = false, UNIFORM = false;
+    static __device__ __forceinline__ uint32_t add(const pb_xlargs &) { return PB_XL_ADD; }
+    static __device__ __forceinline__ uint32_t split(const pb_xlargs &) { return 0u; }
+    static __device__ __forceinline__ uint32_t hdw(const pb_xlargs &) { return PB_XL_TDW; }
+    static __device__ __forceinline__ uint32_t stride(const pb_xlargs &) { return PB_XL_HDW; }
+
+    template <bool VAR>
+    static __device__ __forceinline__ uint32_t header(const pb_xlargs &A, const uint32_t *w, uint64_t so, uint32_t L,
+                                                      uint32_t (&T)[TN])
+    {
+        // source bytes 0..51 as G[u] = bytes 4u .. 4u + 3, from aligned dwords that start inside the frame
+        const uint64_t i = so >> 2, end = so + L;
+        const uint32_t sh = (uint32_t)so & 3u;
+        uint32_t d[14], G[13];
+#pragma unroll
+        for (int t = 0; t < 14; ++t)
+            d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
+#pragma unroll
+        for (int t = 0; t < 13; ++t)
+            G[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
+        const uint32_t tc = G[3] >> 24, proto = G[5] >> 24;
+        uint32_t fl = A.flow_label;
+        if (A.flags & PB_XL_HASH)
+        {
+            // pbgpu_encap's hash of source bytes 26..37; an ICMP frame has no ports: w2 = 0
+            uint32_t x = __builtin_amdgcn_alignbyte(G[7], G[6], 2) ^ __builtin_amdgcn_alignbyte(G[8], G[7], 2);
+            if (proto != 1u)
+                x ^= __builtin_amdgcn_alignbyte(G[9], G[8], 2);
+            x ^= x >> 16;
+            x *= 0x7FEB352Du;
+            x ^= x >> 15;
+            fl = x & 0xFFFFFu;
+        }
+        T[0] = G[0], T[1] = G[1], T[2] = G[2];
+        T[3] = 0xDD86u | ((0x60u | (tc >> 4)) << 16) | ((((tc & 15u) << 4) | (fl >> 16)) << 24);
+        T[4] = pb_bswap16(fl & 0xFFFFu) | (pb_bswap16(L - 34u) << 16);
+        const uint32_t nh = proto == 1u ? 58u : proto;
+        T[5] = A.tpl[0] | nh | (G[5] & 0x00FF0000u) >> 8; // next header, hop limit = the TTL
+        T[6] = A.tpl[1], T[7] = A.tpl[2];
+        T[8] = A.tpl[3] | (G[6] & 0xFFFF0000u);  // source bytes 26, 27
+        T[9] = A.tpl[4] | (G[7] & 0x0000FFFFu);  // 28, 29
+        T[10] = A.tpl[5], T[11] = A.tpl[6];
+        T[12] = A.tpl[7] | (G[7] & 0xFFFF0000u); // 30, 31
+#pragma unroll
+        for (int t = 0; t < 5; ++t)
+            T[13 + t] = G[8 + t]; // output bytes 52..71 = source bytes 32..51
+        T[18] = 0u;
+        // the patched L4 words, kept in registers over the branches: a store to T[] in each branch
+        // would be merged into one at a run-time index, and T[] would leave the registers
+        uint32_t t13 = G[8], t14 = G[9], t15 = G[10], t17 = G[12], sl;
+        if (proto == 17u)
+        {
+            const uint32_t c = pb_bswap16(G[10] & 0xFFFFu); // source bytes 40, 41
+            uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
+            r = r ? r : 0xFFFFu;
+            t15 = (G[10] & 0xFFFF0000u) | pb_bswap16(r);
+            sl = 62u;
+        }
+        else if (proto == 6u)
+        {
+            const uint32_t c = pb_bswap16(G[12] >> 16); // source bytes 50, 51
+            const uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
+            t17 = (G[12] & 0x0000FFFFu) | (pb_bswap16(r) << 16);
+            sl = 72u;
+        }
+        else
+        {
+            const uint32_t wo = pb_bswap16(G[8] >> 16); // type, code
+            const uint32_t nt = (wo >> 8) == 8u ? 128u : 129u;
+            const uint32_t wn = (nt << 8) | (wo & 0xFFu);
+            const uint32_t c = pb_bswap16(G[9] & 0xFFFFu); // source bytes 36, 37
+            const uint32_t ps = A.ksum + pb_bswap16(G[6] >> 16) + pb_bswap16(G[7] & 0xFFFFu) +
+                                pb_bswap16(G[7] >> 16) + pb_bswap16(G[8] & 0xFFFFu) + (L - 34u) + 58u;
+            const uint32_t r = ~pb_fold((~c & 0xFFFFu) + (~wo & 0xFFFFu) + wn + ps) & 0xFFFFu;
+            t13 = (G[8] & 0xFF00FFFFu) | (nt << 16);
+            t14 = (G[9] & 0xFFFF0000u) | pb_bswap16(r);
+            sl = 58u;
+        }
+        T[13] = t13, T[14] = t14, T[15] = t15, T[17] = t17;
+        return sl;
+    }
+};
+
 template <bool VAR>
 __global__ __launch_bounds__(PB_XL_WT) void pb_xlat_kernel(pb_xlargs A)
 {
@@ -6295,210 +6414,7 @@ __global__ __launch_bounds__(PB_XL_WT) void pb_xlat_kernel(pb_xlargs A)
     __shared__ uint32_t s_rel[PB_XL_WIN];
     // slot i: the head of the i-th record touching the page
     __shared__ uint32_t s_hdr[PB_XL_HREC * PB_XL_HDW];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(A.src);
-    const uint32_t reclen = A.fixed_len + PB_XL_ADD;
-    uint64_t p = ((uint64_t)blockIdx.x * A.per) << 12; // the page's first byte in the output
-    if (p >= A.end16)
-        return;
-    // j0: the record holding the first page's first byte, d0: that byte's offset in the record
-    uint64_t j0 = 0, g0 = 0;
-    if (p > 0)
-        pb_rp_first<VAR>(A.offsets, A.first, A.n, PB_XL_ADD, reclen, p, j0, g0);
-    int32_t d0 = (int32_t)(p - g0);
-    uint64_t offj0 = 0; // variable length: frame first + j0's offset in src, j0 the window's first record
-    bool have_win = false;
-    for (uint32_t it = 0; it < A.per && p < A.end16; ++it, p += 4096u)
-    {
-        // variable length: the window is kept from page to page and moved to the record holding the
-        // page's first byte only when it no longer reaches the record after the page's last byte
-        uint32_t kw = 0; // the window's index of the record holding the page's first byte
-        if (VAR)
-        {
-            if (!have_win || (int64_t)s_rel[PB_XL_WIN - 1u] <= (int64_t)d0 + 4095)
-            {
-                if (have_win)
-                {
-                    const uint32_t lo = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_XL_WIN - 1u);
-                    j0 += lo;
-                    d0 -= (int32_t)s_rel[lo];
-                }
-                __syncthreads(); // the window's readers are done
-                offj0 = pb_rp_refill(s_rel, PB_XL_WIN, PB_XL_WT, A.offsets, A.first, A.n, PB_XL_ADD, j0);
-                have_win = true;
-            }
-            __syncthreads(); // the window is in place, the last page's slot readers are done
-            kw = pb_rp_find(s_rel, (uint32_t)d0, 0u, PB_XL_WIN - 1u);
-        }
-        else
-            __syncthreads(); // the last page's slot readers are done
-        const uint64_t fj0 = VAR ? 0 : (A.first + j0) * A.fixed_len; // fixed length: frame first + j0's offset in src
-
-        // ---- head stage: lane i stages the head of the i-th record touching the page ----
-        if (tid < PB_XL_HREC)
-        {
-            const uint32_t k = kw + tid;
-            bool act;
-            uint32_t rs = 0, rlen = reclen; // the record's start relative to record j0, its length
-            if (VAR)
-            {
-                act = k + 1u < PB_XL_WIN;
-                if (act)
-                {
-                    rs = s_rel[k];
-                    const uint32_t re = s_rel[k + 1u];
-                    act = re != 0xFFFFFFFFu; // entries j0 + k and j0 + k + 1 are at most n
-                    rlen = re - rs;
-                }
-            }
-            else
-            {
-                rs = k * reclen;
-                act = j0 + k < A.n;
-            }
-            if (act && (int64_t)rs < (int64_t)d0 + 4096)
-            {
-                const uint32_t L = rlen - PB_XL_ADD;
-                // source bytes 0..51 as G[u] = bytes 4u .. 4u + 3, from aligned dwords that start inside the frame
-                const uint64_t so = VAR ? offj0 + (rs - PB_XL_ADD * k) : fj0 + (uint64_t)k * A.fixed_len;
-                const uint64_t i = so >> 2, end = so + L;
-                const uint32_t sh = (uint32_t)so & 3u;
-                uint32_t d[14], G[13];
-#pragma unroll
-                for (int t = 0; t < 14; ++t)
-                    d[t] = ((i + t) << 2) < end ? w[i + t] : 0u;
-#pragma unroll
-                for (int t = 0; t < 13; ++t)
-                    G[t] = __builtin_amdgcn_alignbyte(d[t + 1], d[t], sh);
-                const uint32_t tc = G[3] >> 24, proto = G[5] >> 24;
-                uint32_t fl = A.flow_label;
-                if (A.flags & PB_XL_HASH)
-                {
-                    // pbgpu_encap's hash of source bytes 26..37; an ICMP frame has no ports: w2 = 0
-                    uint32_t x = __builtin_amdgcn_alignbyte(G[7], G[6], 2) ^ __builtin_amdgcn_alignbyte(G[8], G[7], 2);
-                    if (proto != 1u)
-                        x ^= __builtin_amdgcn_alignbyte(G[9], G[8], 2);
-                    x ^= x >> 16;
-                    x *= 0x7FEB352Du;
-                    x ^= x >> 15;
-                    fl = x & 0xFFFFFu;
-                }
-                uint32_t T[PB_XL_TDW];
-                T[0] = G[0], T[1] = G[1], T[2] = G[2];
-                T[3] = 0xDD86u | ((0x60u | (tc >> 4)) << 16) | ((((tc & 15u) << 4) | (fl >> 16)) << 24);
-                T[4] = pb_bswap16(fl & 0xFFFFu) | (pb_bswap16(L - 34u) << 16);
-                const uint32_t nh = proto == 1u ? 58u : proto;
-                T[5] = A.tpl[0] | nh | (G[5] & 0x00FF0000u) >> 8; // next header, hop limit = the TTL
-                T[6] = A.tpl[1], T[7] = A.tpl[2];
-                T[8] = A.tpl[3] | (G[6] & 0xFFFF0000u);  // source bytes 26, 27
-                T[9] = A.tpl[4] | (G[7] & 0x0000FFFFu);  // 28, 29
-                T[10] = A.tpl[5], T[11] = A.tpl[6];
-                T[12] = A.tpl[7] | (G[7] & 0xFFFF0000u); // 30, 31
-#pragma unroll
-                for (int t = 0; t < 5; ++t)
-                    T[13 + t] = G[8 + t]; // output bytes 52..71 = source bytes 32..51
-                T[18] = 0u;
-                uint32_t sl;
-                if (proto == 17u)
-                {
-                    const uint32_t c = pb_bswap16(G[10] & 0xFFFFu); // source bytes 40, 41
-                    uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
-                    r = r ? r : 0xFFFFu;
-                    T[15] = (G[10] & 0xFFFF0000u) | pb_bswap16(r);
-                    sl = 62u;
-                }
-                else if (proto == 6u)
-                {
-                    const uint32_t c = pb_bswap16(G[12] >> 16); // source bytes 50, 51
-                    const uint32_t r = ~pb_fold((~c & 0xFFFFu) + A.ksum) & 0xFFFFu;
-                    T[17] = (G[12] & 0x0000FFFFu) | (pb_bswap16(r) << 16);
-                    sl = 72u;
-                }
-                else
-                {
-                    const uint32_t wo = pb_bswap16(G[8] >> 16); // type, code
-                    const uint32_t nt = (wo >> 8) == 8u ? 128u : 129u;
-                    const uint32_t wn = (nt << 8) | (wo & 0xFFu);
-                    const uint32_t c = pb_bswap16(G[9] & 0xFFFFu); // source bytes 36, 37
-                    const uint32_t ps = A.ksum + pb_bswap16(G[6] >> 16) + pb_bswap16(G[7] & 0xFFFFu) +
-                                        pb_bswap16(G[7] >> 16) + pb_bswap16(G[8] & 0xFFFFu) + (L - 34u) + 58u;
-                    const uint32_t r = ~pb_fold((~c & 0xFFFFu) + (~wo & 0xFFFFu) + wn + ps) & 0xFFFFu;
-                    T[13] = (G[8] & 0xFF00FFFFu) | (nt << 16);
-                    T[14] = (G[9] & 0xFFFF0000u) | pb_bswap16(r);
-                    sl = 58u;
-                }
-                const int32_t hs = (int32_t)rs - d0; // the record's first byte in the page (below 0: before it)
-                uint32_t *slot = s_hdr + tid * PB_XL_HDW;
-                pb_rp_stage(slot, T, PB_XL_TDW, (uint32_t)hs & 3u);
-                slot[PB_XL_TDW] = sl;
-            }
-        }
-        __syncthreads();
-
-        // ---- chunks ----
-        const int32_t d = d0 + 16 * (int32_t)tid;
-        const uint64_t pc = p + 16u * tid;
-        if (pc < A.end16)
-        {
-            // k, r: the chunk starts r bytes into record j0 + k, which is ea bytes long; pc is
-            // below the output's last byte, so that record is inside the range
-            uint32_t k, rs, ea;
-            if (VAR)
-            {
-                k = pb_rp_find(s_rel, (uint32_t)d, 0u, PB_XL_WIN - 1u);
-                rs = s_rel[k];
-                ea = s_rel[k + 1u] - rs;
-            }
-            else
-            {
-                k = pb_divq((uint32_t)d, A.rec);
-                rs = k * reclen;
-                ea = reclen;
-            }
-            const int32_t r = d - (int32_t)rs;
-            const bool bvalid = j0 + k + 1u < A.n; // a next record: its first bytes may end the chunk
-            // the record's byte b >= its staged length is source byte offa + b
-            const int64_t offa =
-                (int64_t)(VAR ? offj0 + (rs - PB_XL_ADD * k) : fj0 + (uint64_t)k * A.fixed_len) - (int64_t)PB_XL_ADD;
-            const uint32_t ia = k - kw; // the record's slot; the next record's is the one after
-            const int32_t sl = (int32_t)s_hdr[ia * PB_XL_HDW + PB_XL_TDW];
-            const int32_t e3 = (int32_t)ea;
-            pb_u32x4 v;
-            if (__ballot(!(r >= sl && r + 16 <= e3)) == 0ull)
-                v = pb_rp_copy16(w, (uint64_t)(offa + r));
-            else
-            {
-                uint32_t s1[4];
-                {
-                    const int32_t lo = (r > sl ? r : sl) - r;
-                    const int32_t hi = (r + 16 < e3 ? r + 16 : e3) - r;
-                    pb_rp_gather(w, offa + r, lo, hi, s1);
-                }
-                const int32_t hsa = (int32_t)rs - d0, hsb = hsa + (int32_t)ea;
-                const int32_t q = 16 * (int32_t)tid;
-                const int32_t ua = (q - (hsa & ~3)) >> 2, ub = (q - (hsb & ~3)) >> 2;
-                uint32_t o4[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                {
-                    const uint32_t va = (uint32_t)(ua + t) < PB_XL_TDW ? s_hdr[ia * PB_XL_HDW + (uint32_t)(ua + t)] : 0u;
-                    const uint32_t vb = bvalid && (uint32_t)(ub + t) < PB_XL_TDW
-                                            ? s_hdr[(ia + 1u) * PB_XL_HDW + (uint32_t)(ub + t)]
-                                            : 0u;
-                    const int32_t o = r + 4 * t;
-                    const uint32_t m1 = pb_rp_lt(o, sl), m3 = pb_rp_lt(o, e3);
-                    o4[t] = (va & m1) | (s1[t] & m3 & ~m1) | (vb & ~m3);
-                }
-                v = pb_u32x4{o4[0], o4[1], o4[2], o4[3]};
-            }
-            *reinterpret_cast<pb_u32x4 *>(A.dst + pc) = v;
-        }
-        // the next page's first byte: 4096 on in the same window, or a whole number of records on
-        if (VAR)
-            d0 += 4096;
-        else
-            pb_rp_next_page(d0, j0, A.rec, reclen);
-    }
+    pb_ins_write<pb_xl_kind, VAR>(A, s_rel, s_hdr);
 }
 
 // stage 0: the result words and the classify pass; stage 1: dst->offsets (variable length, by
@@ -6509,7 +6425,7 @@ extern "C" hipError_t pbk_launch_xlat(const pb_xlargs *A, int stage, uint32_t gr
     {
         const uint64_t per = (uint64_t)PB_XL_WT * PB_XL_ROWS;
         const uint32_t cg = (uint32_t)((A->n + per - 1u) / per);
-        hipLaunchKernelGGL(pb_xlat_init_kernel, dim3(1), dim3(64), 0, st, A->res);
+        hipLaunchKernelGGL(pb_res_init_kernel, dim3(1), dim3(64), 0, st, A->res, PB_XL_RES_DW, ~0ull);
         if (A->offsets)
             hipLaunchKernelGGL((pb_xlat_class_kernel<true>), dim3(cg), dim3(PB_XL_WT), 0, st, *A);
         else

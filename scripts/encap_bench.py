@@ -28,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import pb_configs as pc  # noqa: E402
 import pyencap  # noqa: E402
+import pbgpu  # noqa: E402
 from pbgpu import ENCAP_VLAN, ENCAP_VXLAN, EncapOpts, GpuContext, Sequence  # noqa: E402
 
 CONFIGS = ["c2_udp_64:vxlan", "c4_tcp_syn:vxlan", "c2_udp_1500:vxlan", "c3_udp_var:vxlan", "c2_udp_64:vlan"]
@@ -127,9 +128,10 @@ def main():
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--meta")
+    ap.add_argument("--lib", default=pbgpu.LIB_PATH, help="another build of libpbgpu.so (side-by-side A/B)")
     a = ap.parse_args()
     lines = []
-    with GpuContext(0) as ctx:
+    with GpuContext(0, a.lib) as ctx:
         for item in a.configs.split(","):
             name, mode = item.split(":")
             r = run(ctx, name, mode, 1 << a.log2, a.reps, a.warmup, a.pmc)

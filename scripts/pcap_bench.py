@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pb-af-xdp_amd"))
 
 import pb_configs as pc  # noqa: E402
+import pbgpu  # noqa: E402
 from pbgpu import GpuContext, Sequence  # noqa: E402
 
 CONFIGS = ["c2_udp_64", "c4_tcp_syn", "c2_udp_1500", "c3_udp_var"]
@@ -113,9 +114,10 @@ def main():
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--meta")
+    ap.add_argument("--lib", default=pbgpu.LIB_PATH, help="another build of libpbgpu.so (side-by-side A/B)")
     a = ap.parse_args()
     lines = []
-    with GpuContext(0) as ctx:
+    with GpuContext(0, a.lib) as ctx:
         for name in a.configs.split(","):
             r = run(ctx, name, 1 << a.log2, a.reps, a.warmup, a.pmc)
             print(json.dumps(r), flush=True)

@@ -123,9 +123,10 @@ def main():
     ap.add_argument("--rows", default=",".join(ROWS))
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--meta")
+    ap.add_argument("--lib", default=pbgpu.LIB_PATH, help="another build of libpbgpu.so (side-by-side A/B)")
     a = ap.parse_args()
     lines = []
-    with GpuContext(0) as ctx:
+    with GpuContext(0, a.lib) as ctx:
         for row in a.rows.split(","):
             r = run(ctx, row, a.log2, a.reps, a.warmup, a.pmc)
             print(json.dumps(r), flush=True)

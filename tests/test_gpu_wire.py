@@ -495,3 +495,54 @@ def test_inner_payload_flip_is_seen_here_only(ctx):
     finally:
         fb.free()
         vx.free()
+
+
+# ------------------------------------------------------------------ 8. both verifiers on one context
+def test_both_verifiers_take_turns_on_one_context(ctx):
+    """pbgpu_verify and pbgpu_verify_wire share one record scratch and one mapped result buffer; their
+    records have 5 and 11 counts.  Three buffers on one context: 4,096 frames of 64 B with mutants (19
+    workgroups of the wire verifier, 64 waves of the page verifier), 8 clean frames of 1500 B (one
+    workgroup in both) and 300 packed frames of c3_udp_var; the calls alternate, each with codes, and
+    every result and code array is compared with its reference: a stale count, a stale first_bad or a
+    record read at the other call's stride shows as a wrong count.  Every failure count of both calls
+    is nonzero on the first buffer except pbgpu_verify's bad_short, which no frame of 64 B can raise."""
+    def built(cfg, n):
+        ctx.load_sequence(0, Sequence.from_config(pc.get(cfg)), pc.SEED_BASE)
+        fb = ctx.alloc_frames(*ctx.build_size(0, n))
+        ctx.build(0, 0, n, fb)
+        return fb
+
+    bufs = [built("c2_udp_64", 4096), built("c2_udp_1500", 8), built("c3_udp_var", 300)]
+    try:
+        a = bufs[0]
+        assert [int(b.f.fixed_len) for b in bufs] == [64, 1500, 0]
+        assert wire_shape(64, 4096)["grid"] == 19 and vr.verify_shape(64, 0, 4096, 64)["grid"] == 64
+        assert wire_shape(1500, 8)["grid"] == 1 and vr.verify_shape(1500, 0, 8, 1500)["grid"] == 1
+        data = a.packed().copy()
+        for k, f in enumerate((5, 700, 2045, 3333, 4090)):  # in several workgroups and pages, not frame 0
+            o = f * 64
+            data[o + 22] ^= 0x01 << k              # TTL: the IPv4 checksum
+            data[o + 64 + 17] ^= 0x04              # the next frame's tot_len (and its IPv4 checksum)
+            data[o + 128 + 63 - k] ^= 0x80         # a payload byte: the L4 checksum
+            data[o + 192 + 39] ^= 0x02             # the UDP length (and the L4 checksum)
+            data[o + 256 + 14] = 0x55              # version 5: malformed as sent, a wrong IPv4 sum to pbgpu_verify
+        a.upload(data, fixed_len=64)
+        refs = []
+        for b in bufs:
+            d, off = b.packed(), b.offsets()
+            frames = [d[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(off) - 1)]
+            refs.append((vr.ref_codes(d, off),) + reference(frames))
+        v0, w0, _ = refs[0]
+        assert all(np.count_nonzero(v0 & bit) for bit in (1, 2, 4)) and all(np.count_nonzero(w0 & bit) for bit in (1, 2, 4, 8, 16))
+        assert v0[0] == 0 and w0[0] == 0 and not refs[1][0].any() and not (refs[1][1] & pw.BAD).any()
+        for call, i in (("wire", 0), ("verify", 1), ("wire", 1), ("verify", 0), ("wire", 2), ("verify", 2), ("wire", 0)):
+            vref, wref, l3 = refs[i]
+            if call == "wire":
+                res, codes = bufs[i].verify_wire(vxlan_port=PORT, codes=True)
+                expect(res, codes, wref, l3)
+            else:
+                res, codes = bufs[i].verify(codes=True)
+                vr.expect(res, codes, vref)
+    finally:
+        for b in bufs:
+            b.free()
